@@ -2,8 +2,12 @@
 """Headline benchmark: attention forward TFLOPS/GPU, bf16, seqlen=4096, hdim=128, causal
 (BASELINE.json configs[2], the Llama-3-8B shape B=16 H=32), on synthetic N(0,1) tensors.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds the supplementary
+measurements (other shapes and kernels, decode rooflines, the library GEMM, the CPU baseline, configs[4]'s shard
+under --gpus N > 1).  --dump-outputs DIR writes what the last timed step computed (dump_outputs()).
 
 Started without a launcher (WORLD_SIZE unset) and --gpus N > 1, it launches itself: N fresh child
 processes through torch.distributed.run, before this process has touched a GPU; rank 0's JSON line is
@@ -257,6 +261,23 @@ def measure_traffic(timeout_s=150):
     return total, "measured in this run: rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE over tools/prefill_once.py (same kernel, same shape), per launch"
 
 
+def dump_outputs(path, out):
+    """--dump-outputs DIR: the output tensor of the last timed step (what flash_attn_fwd returns), sampled at fixed,
+    seeded positions and written as float32: out_heads.npy = 8 whole (batch, head) slices [8, S, D] and
+    out_sample.npy = 2**21 elements at random flat indices of the whole [B, H, S, D] tensor (24 MiB in all).  The inputs
+    are seeded too, so two builds run with the same arguments can be compared file for file."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    B, H, S, D = out.shape
+    rng = np.random.default_rng(2024)
+    bh = torch.from_numpy(np.sort(rng.choice(B * H, size=8, replace=False))).to(out.device)
+    idx = torch.from_numpy(np.sort(rng.integers(0, out.numel(), size=1 << 21))).to(out.device)
+    flat = out.contiguous().view(-1)
+    np.save(os.path.join(path, "out_heads.npy"), flat.view(B * H, S, D)[bh].float().cpu().numpy())
+    np.save(os.path.join(path, "out_sample.npy"), flat[idx].float().cpu().numpy())
+
+
 def self_launch(args, argv):
     """--gpus N > 1 without a launcher: start N fresh ranks (torch.distributed.run) and relay their output.
     Nothing in THIS process has touched a GPU yet (torch is not even imported), and it is never replaced by
@@ -276,11 +297,16 @@ def main():
     # 6 % slower (10 steps after 3 warm-ups: 997 TFLOPS; 100 after 20: 1058 on the same device)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=30)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-decode", action="store_true")
-    ap.add_argument("--no-config5", action="store_true", help="skip the configs[4] shard under --gpus N > 1")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the supplementary measurements (off by default)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="under --full: skip the CPU baseline")
+    ap.add_argument("--no-decode", action="store_true",
+                    help="under --full: skip the supplementary GPU workloads of a one-GPU run")
+    ap.add_argument("--no-config5", action="store_true", help="under --full: skip the configs[4] shard under --gpus N > 1")
     ap.add_argument("--measure-traffic", action="store_true",
                     help="measure roofline.traffic now (two rocprofv3 --pmc child runs, ~40 s) instead of citing profiles/")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's output (a fixed sample, float32 .npy) under DIR")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args, sys.argv[1:]))
@@ -341,10 +367,12 @@ def main():
     from starflashattention_amd.sharding import aggregate_throughput, gather_over_ranks, max_over_ranks
     per_rank_ms = gather_over_ranks(elapsed / args.steps * 1e3, dist, dev)     # (devices of one node differ by several %)
     elapsed = max_over_ranks(elapsed, dist, dev)          # the job is as slow as its slowest rank
+    if args.dump_outputs and rank == 0:                   # before anything below reuses `out`
+        dump_outputs(args.dump_outputs, out)
     # BASELINE.json configs[4] is the multi-GPU workload proper (B=128 S=8192 non-causal over 8 GPUs = B=16 per GPU):
-    # under --gpus N every rank also times its shard of it; still no data-path collective
+    # under --gpus N --full every rank also times its shard of it; still no data-path collective
     c5 = None
-    if world > 1 and not args.no_config5:
+    if world > 1 and args.full and not args.no_config5:
         c5_steps = min(10, max(3, args.steps // 4))
         if dist is not None:
             dist.barrier()
@@ -404,7 +432,7 @@ def main():
                               "kernel": c5_name, "tflops_total": round(tot, 2), "tflops_per_gpu": round(tot / world, 2),
                               "frac_mfma_peak": round(tot / world / PEAK_BF16_TFLOPS, 4)}
             rec["per_rank_ms"]["config5"] = [round(x, 4) for x in c5_all]
-        if world == 1:
+        if world == 1 and args.full:
             # supplementary, NOT the headline: the opt-in prescaled-Q kernels (fast_scale=True)
             try:
                 fs = lambda: sfa.flash_attn_fwd(q, k, v, causal=causal, out=out, fast_scale=True)
@@ -422,7 +450,7 @@ def main():
                     "note": "opt-in fast_scale=True (Q*scale rounded to bf16 once; not the default path)"}
             except Exception as e:
                 rec["fast_scale_variant"] = {"error": repr(e)[:200]}
-        if world == 1 and not args.no_decode:
+        if world == 1 and args.full and not args.no_decode:
             try:
                 del q, k, v, out
                 torch.cuda.empty_cache()
@@ -453,7 +481,7 @@ def main():
                                         "frac_mfma_peak": round(tf / PEAK_BF16_TFLOPS, 4)}
             except Exception as e:
                 rec["headline_warm"] = {"error": repr(e)[:200]}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline(torch)
         print(json.dumps(rec), flush=True)
     if dist is not None:

@@ -28,7 +28,7 @@ def run_bench(*extra, env=None):
 
 
 def test_bench_two_ranks_self_launch():
-    rec = run_bench("--gpus", "2", env={"SFA_BENCH_BACKEND": "gloo"})
+    rec = run_bench("--gpus", "2", "--full", env={"SFA_BENCH_BACKEND": "gloo"})
     assert rec["n_gpus"] == 2 and rec["steps"] == 3 and rec["warmup"] == 1
     assert rec["config"]["global_batch"] == 32 and rec["scaling"] == "weak"
     assert rec["unit"] == "TFLOPS" and rec["dtype"] == "bf16" and rec["vs_baseline"] is None
@@ -44,9 +44,18 @@ def test_bench_two_ranks_self_launch():
     assert "prefill_w4_kernel" in rec["roofline"]["kernel"] and "prefill_w4_kernel" in c5["kernel"]
 
 
-def test_bench_single_rank_line():
-    rec = run_bench()
+def test_bench_single_rank_line(tmp_path):
+    """A plain run: the headline only (no supplementary keys without --full), and --dump-outputs writes the last timed
+    step's output as float32 .npy files within 64 MB."""
+    rec = run_bench("--dump-outputs", str(tmp_path))
     assert rec["n_gpus"] == 1 and rec["config"]["global_batch"] == 16
+    assert rec["higher_is_better"] is True and rec["dtype"] == "bf16" and rec["ms_per_step"] > 0
+    assert not {"fast_scale_variant", "config5_shard", "decode_roofline", "gemm_calibration", "cpu_baseline"} & set(rec)
+    import numpy as np
+    heads, sample = np.load(tmp_path / "out_heads.npy"), np.load(tmp_path / "out_sample.npy")
+    assert heads.dtype == np.float32 and heads.shape == (8, 4096, 128) and sample.dtype == np.float32
+    assert heads.nbytes + sample.nbytes <= 64 << 20
+    assert np.isfinite(heads).all() and np.isfinite(sample).all() and heads.std() > 0
     rf = rec["roofline"]
     assert rf["bound"] == "mfma" and rf["peak"] == 2500.0 and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-3
     assert 100.0 < rec["value"] < 2500.0

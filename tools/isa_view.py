@@ -4,13 +4,14 @@ usage: tools/isa_view.py file.hip|file.s <kernel-substring> [extra hipcc flags]
 M mfma | x v_exp | v other VALU | a v_accvgpr_* | L v_readlane/v_writelane (SGPR spill traffic) |
 r ds_read | w ds_write | g global/buffer load | D LDS-DMA | G store | c s_waitcnt | B s_barrier |
 s other SALU | p permlane/dpp | j branch | n s_nop | ! scratch"""
-import re, subprocess, sys
+import os, re, subprocess, sys
 src, pat = sys.argv[1], sys.argv[2]
 flags = sys.argv[3:]
 if src.endswith(".s"):
     asm = open(src).read()
 else:
-    asm = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-I/root/repo",
+    asm = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950",
+                          "-I" + os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                           "-S", "--cuda-device-only", src, "-o", "-"] + flags, capture_output=True, text=True).stdout
 lines = asm.split("\n")
 start = None

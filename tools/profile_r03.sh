@@ -8,7 +8,7 @@ cd "${GRAFT_REPO_ROOT:-.}"
 ROOT=$PWD
 OUT=$ROOT/gpurun_out/profile; rm -rf $OUT; mkdir -p $OUT
 WARM=20
-ARGS="--steps 100 --warmup $WARM --no-cpu-baseline --no-decode"
+ARGS="--steps 100 --warmup $WARM --full --no-cpu-baseline --no-decode"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python $ROOT/bench.py $ARGS > $OUT/trace.log 2>&1 < /dev/null
 echo "trace rc=$?"; tail -1 $OUT/trace.log | cut -c1-600
