@@ -208,9 +208,11 @@ int sfa_prefill_fwd(const sfa_prefill_args *args, void *stream);
 
 /* ---- test / A-B hooks: NOT part of the drop-in surface ------------------------------ */
 /* The launch paths read no environment variable; the test-suite and tools/ select kernel
- * variants through this call.  knob: "prefill_impl" (-1 auto; kernel generation, see
+ * variants through this call.  knob: "prefill_impl" (-1 auto; the kernel ids of csrc/prefill_common.h, see
  * csrc/prefill_dispatch.hip), "prefill_pairs" (1/2), "decode_nt" (0/1), "decode_gqa_mfma" (0/1),
- * "bm128_one_wg" (0/1).  value -1 = the library's own choice.  Process-wide. */
+ * "bm128_one_wg" (0/1).  value -1 = the library's own choice.  Process-wide.  The diagnostic values -- prefill_impl
+ * 2, 4, 43, 44 and bm128_one_wg 1 -- need the diagnostics build of the library (build_lib(variants=True)); elsewhere
+ * sfa_debug_set refuses bm128_one_wg 1 and sfa_prefill_fwd refuses those ids, as it refuses any id not in the table. */
 int sfa_debug_set(const char *knob, int value);
 /* Read back: the knobs above, and "last_prefill_kernel" = which kernel the last sfa_prefill_fwd of this process
  * launched (the dispatcher's choice included): 1 / 3 the 8-wave 256-row kernel (exact / prescaled), 20 + f the 128-row

@@ -6,8 +6,8 @@ import ctypes
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# SFA_LIB_PATH: load another build of the same ABI instead (the A/B library with the earlier kernel
-# generations, libStarFlashAttention_ab.so -- pytest -m variants, tools/prefill_ab.py)
+# SFA_LIB_PATH: load another build of the same ABI instead (the A/B library with the diagnostic builds of the
+# shipping kernels, libStarFlashAttention_ab.so -- tools/prefill_stamps.py, tools/w4_seam_stamps.py, tools/lib_ab.sh)
 LIB_PATH = os.environ.get("SFA_LIB_PATH") or os.path.join(_HERE, "lib", "libStarFlashAttention.so")
 
 SFA_OK = 0

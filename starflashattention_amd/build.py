@@ -30,10 +30,9 @@ KERNEL_SOURCES = ["prefill_w4_kernel.hip", "prefill_w4_kernel_p1.hip", "prefill_
                   "prefill_w4d_kernel.hip", "decode_kernel.hip", "decode_gqa_kernel.hip", "decode_gqa_mfma_kernel.hip", "prefill_d256_kernel.hip",
                   "prefill_kernel.hip", "prefill_kernel_bm128.hip", "prefill_dispatch.hip",
                   "aux_kernels.hip", "c_api.hip", "cxx_surface.hip"]
-# Earlier kernel generations kept for A/B runs (tools/prefill_ab.py, pytest -m variants).  They are never an
-# auto choice of launch_prefill, so the shipping library does not carry them: build_lib(variants=True)
-# compiles them (and -DSFA_WITH_VARIANTS) into a second library, libStarFlashAttention_ab.so.
-VARIANT_SOURCES = ["prefill_kernel16.hip", "prefill_baseline.hip", "prefill_w4r2_kernel.hip"]
+# The diagnostic builds of the shipping kernels (stamping / event-log builds, prefill_common.h) are never an auto
+# choice of launch_prefill, so the shipping library does not carry them: build_lib(variants=True) compiles the same
+# sources with -DSFA_WITH_VARIANTS into a second library, libStarFlashAttention_ab.so (SFA_LIB_PATH selects it).
 AB_LIB_NAME = "libStarFlashAttention_ab.so"
 
 
@@ -70,13 +69,12 @@ def _headers():
 
 def build_lib(force=False, verbose=False, extra_flags=(), variants=False):
     """hipcc -> starflashattention_amd/lib/libStarFlashAttention.so; returns its path.
-    variants=True builds the A/B library (earlier kernel generations included) next to it instead."""
+    variants=True builds the A/B library (the diagnostic builds of the shipping kernels included) next to it instead."""
     objdir = OBJDIR + ("_ab" if variants else "")
     os.makedirs(LIBDIR, exist_ok=True)
     os.makedirs(objdir, exist_ok=True)
     out = os.path.join(LIBDIR, AB_LIB_NAME if variants else LIB_NAME)
-    names = KERNEL_SOURCES + (VARIANT_SOURCES if variants else [])
-    srcs = [os.path.join(CSRC, s) for s in names]
+    srcs = [os.path.join(CSRC, s) for s in KERNEL_SOURCES]
     flags = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I" + ROOT,
              "-Wall", "-Wno-unused-function"] + (["-DSFA_WITH_VARIANTS=1"] if variants else []) + list(extra_flags)
     stamp = _stamp(srcs + _headers(), " ".join(flags) + repr(sorted(EXTRA_FLAGS.items())))

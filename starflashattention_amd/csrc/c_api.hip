@@ -92,6 +92,10 @@ int sfa_debug_set(const char *knob, int value) {
     else if (!strcmp(knob, "decode_gqa_mfma")) k = &g_knobs.decode_gqa_mfma;
     else if (!strcmp(knob, "bm128_one_wg")) k = &g_knobs.bm128_one_wg;
     else return fail(SFA_ERR_BAD_SHAPE, "sfa_debug_set: unknown knob '%s'", knob);
+#ifndef SFA_WITH_VARIANTS
+    if (k == &g_knobs.bm128_one_wg && value > 0)
+        return fail(SFA_ERR_BAD_SHAPE, "sfa_debug_set: bm128_one_wg %d needs the diagnostics build of the library", value);
+#endif
     k->store(value, std::memory_order_relaxed);
     return SFA_OK;
 }

@@ -1,8 +1,7 @@
 // Grouped-query decode on the matrix cores, for groups too large for the VALU kernel
 // (decode_gqa_kernel.hip is VALU-bound from 8 query heads per kv head on: 4.1 of 6.5 TB/s).
 // One workgroup per (batch, kv head, split), four waves, each wave walks its share of the cached rows
-// in 32-key tiles with the fragment maps of prefill_core16.h (v_mfma_f32_16x16x32, 16 query columns of
-// which G are real):
+// in 32-key tiles on v_mfma_f32_16x16x32 (16 query columns of which G are real):
 //   S^T[key][q] = K . Q^T     A = K rows: head-major caches are read from HBM DIRECTLY in operand layout
 //                                 (lane (c = l & 15, g = l >> 4) loads K[t + 16kt + c][32ks + 8g .. +8]);
 //                                 the reference layout is read row-major and re-laid out through a
@@ -18,17 +17,30 @@
 #include <cstdlib>
 
 #include "decode_common.h"
-#include "prefill_core16.h"
 
 namespace sfa {
 
 namespace {
 
 using namespace decode;
-using prefill::Mfma16;
-using prefill::quad_max;
-using prefill::quad_sum;
-using prefill::lds_i16x4;
+
+typedef __attribute__((address_space(3))) i16x4 lds_i16x4;
+
+template <class Tr> struct Mfma16;
+template <> struct Mfma16<Bf16> {
+    static __device__ __forceinline__ f32x4 run(bf16x8 a, bf16x8 b, f32x4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+    }
+};
+template <> struct Mfma16<Fp16> {
+    static __device__ __forceinline__ f32x4 run(f16x8 a, f16x8 b, f32x4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+    }
+};
+
+// max / sum over the four lanes {c, c+16, c+32, c+48} that share a query
+__device__ __forceinline__ float quad_max(float x) { return row_pair_max(half_max(x)); }
+__device__ __forceinline__ float quad_sum(float x) { return row_pair_sum(half_sum(x)); }
 
 constexpr int kTile = 32;                       // keys per tile
 

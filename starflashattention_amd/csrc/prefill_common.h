@@ -1,5 +1,5 @@
-// Shared pieces of the gfx950 prefill kernels: tile geometry, the XOR-swizzled LDS images of the
-// baseline generation and the block -> (head, q-tile) map.  Design notes: prefill_kernel.hip.
+// Shared pieces of the gfx950 prefill kernels: tile geometry, the block -> (head, q-tile) map, the
+// prefill_impl table and the launchers.  Design notes: prefill_kernel.hip.
 #pragma once
 #include "sfa_device.h"
 #include "sfa_host.h"
@@ -12,18 +12,6 @@ constexpr int kBN = 64;       // keys per tile
 constexpr int kThreads = 512;
 
 __device__ __forceinline__ float ninf() { return -__builtin_huge_valf(); }
-
-// byte offset of 16-byte chunk `ch` of row `row` inside a [kBN][D] 16-bit LDS tile
-template <int D>
-__device__ __forceinline__ int k_off(int row, int ch) {
-    if (D == 128) return 256 * row + 16 * (ch ^ (row & 15));
-    return 128 * row + 16 * (ch ^ ((row >> 1) & 7));
-}
-template <int D>
-__device__ __forceinline__ int v_off(int row, int ch) {
-    if (D == 128) return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
-    return 128 * row + 16 * (ch ^ (((row >> 1) & 1) << 2));
-}
 
 typedef __attribute__((address_space(3))) i16x4 lds_i16x4;
 
@@ -42,16 +30,26 @@ __device__ __forceinline__ BlockCoord block_coord(const PrefillKernelParams &p) 
 
 }  // namespace prefill
 
-// the product kernel and the baseline generation kept for A/B runs; launch_prefill picks one
-int launch_prefill_main(const PrefillKernelParams &p, int dtype, int head_dim, bool causal, hipStream_t stream);
-int launch_prefill_variant(int which, const PrefillKernelParams &p, int dtype, int head_dim, bool causal,
-                           hipStream_t stream);
+// sfa_debug_set("prefill_impl", id): the kernel launch_prefill runs (prefill_dispatch.hip).  Stable ids: tests, tools/,
+// profiles/ and sfa_debug_get("last_prefill_kernel") cite them.  The diagnostic builds are in the A/B library only.
+enum PrefillImpl : int {
+    kPrefillAuto = -1,
+    kPrefill8w = 1, kPrefill8wPrescaled = 3, kPrefill8wExact = 10,      // 8-wave 256-row kernel: by policy / forced
+    kPrefill8wUnstaged = 2,                 // diagnostic: un-staged softmax slices (tools/prefill_ab.py)
+    kPrefill8wStamps = 4,                   // diagnostic: in-kernel stamps into the lse buffer (tools/prefill_*stamps.py)
+    kPrefillBm128 = 20, kPrefillBm128Prescaled = 21, kPrefillBm128Exact = 22,      // 128-row kernel
+    kPrefillW4 = 40, kPrefillW4Prescaled = 41, kPrefillW4Exact = 42,    // 4-wave persistent kernel
+    kPrefillW4Stamps = 43,                  // diagnostic: q-tile stamps into the lse buffer (tools/w4_seam_stamps.py)
+    kPrefillW4Events = 44,                  // diagnostic: event log into the lse buffer (tools/w4_events.py)
+    kPrefillD256W4 = 60, kPrefillD256 = 61, // head_dim 256: persistent kernel / compiler-scheduled fallback
+};
+
+// The launchers of the 8-wave, 128-row and 4-wave kernels.  force: 0 = flavour by policy (exact unless the caller opted
+// into fast_scale), 1 = prescaled, 2 = exact; 3 / 4 = the diagnostic builds (A/B library only) of the enum above.
+int launch_prefill_main(const PrefillKernelParams &p, int dtype, int head_dim, bool causal, hipStream_t stream,
+                        int force = 0);
 int launch_prefill_bm128(const PrefillKernelParams &p, int dtype, int head_dim, bool causal, hipStream_t stream,
                          int force = 0);
-int launch_prefill_x16(const PrefillKernelParams &p, int dtype, int head_dim, bool causal, hipStream_t stream,
-                       int force = 0);
-int launch_prefill_baseline(const PrefillKernelParams &p, int dtype, int head_dim, bool causal, hipStream_t stream);
-// the 4-wave persistent kernel (prefill_w4_kernel.hip); force: 0 = flavour by policy, 1 = prescaled, 2 = exact
 int launch_prefill_w4(const PrefillKernelParams &p, int dtype, int head_dim, bool causal, hipStream_t stream,
                       int force = 0);
 // whether one head's Q / K / V rows fit the 32-bit buffer descriptors of the 4-wave kernel (else: the 8-wave kernel)
@@ -61,10 +59,6 @@ bool prefill_w4_serves(const PrefillKernelParams &p, int head_dim);
 int launch_prefill_w4_fp16_exact(const PrefillKernelParams &p, bool causal, hipStream_t stream);
 int launch_prefill_w4_fp16_prescaled(const PrefillKernelParams &p, bool causal, hipStream_t stream);
 int launch_prefill_w4_bf16_prescaled(const PrefillKernelParams &p, bool causal, hipStream_t stream);
-// round 2's generation of the 4-wave kernel (q-tiles scored and finished outside the pipeline) and its stamping /
-// ablation builds: the A/B library only (prefill_w4r2_kernel.hip)
-int launch_prefill_w4r2(const PrefillKernelParams &p, int dtype, int head_dim, bool causal, hipStream_t stream,
-                        int force = 0);
 // head_dim 256: the one-wave-per-SIMD persistent kernel (prefill_w4d_kernel.hip) wherever one head's rows fit its
 // 32-bit buffer descriptors, the compiler-scheduled kernel (prefill_d256_kernel.hip) otherwise
 int launch_prefill_w4d(const PrefillKernelParams &p, int dtype, bool causal, hipStream_t stream);

@@ -46,7 +46,7 @@
 //     is gone: +5 %; opt-in, sfa_prefill_args.fast_scale).  launch_prefill_main picks.
 //   * Where the K/V tiles of a stream position live is computed once per step on the scalar unit
 //     (tile_src), not inside every staging load.
-//   * LDS images use PADDED rows (prefill_common.h would XOR-swizzle): every read address is one
+//   * LDS images use PADDED rows, not XOR-swizzled ones: every read address is one
 //     lane-constant base plus a compile-time immediate -- two LDS address registers in total --
 //     and SQ_LDS_BANK_CONFLICT measures 0.
 //   * One workgroup processes a PAIR of q-tiles of the same (batch, head): the heaviest remaining
@@ -466,20 +466,17 @@ int launch_cfg(const PrefillKernelParams &p, int dtype, int head_dim, bool causa
 // (sfa_prefill_args.fast_scale) and wants no log-sum-exp: its scores carry Q*scale rounded to 16 bit --
 // O within one 16-bit rounding of the exact kernel's for unit-variance data, but the score error grows
 // with the logits (tests/test_prefill_gpu.py::test_prefill_extreme_logits).
-int launch_prefill_main(const PrefillKernelParams &p, int dtype, int head_dim, bool causal, hipStream_t stream) {
-    if (p.fast_scale) return launch_cfg<2, 6, 0>(p, dtype, head_dim, causal, stream);
-    return launch_cfg<2, 2, 0>(p, dtype, head_dim, causal, stream);     // prefetch distance 2, staged softmax
-}
-// forced / diagnostic variants for the tests, tools/prefill_ab.py and tools/prefill_*stamps.py
-int launch_prefill_variant(int which, const PrefillKernelParams &p, int dtype, int head_dim, bool causal,
-                           hipStream_t stream) {
-#ifdef SFA_WITH_VARIANTS      // diagnostics: the A/B library only
-    if (which == 2) return launch_cfg<2, 0, 0>(p, dtype, head_dim, causal, stream);     // un-staged softmax slices
-    if (which == 4) return launch_cfg<2, 2, 2>(p, dtype, head_dim, causal, stream);     // in-kernel stamps -> lse buffer
+// force: prefill_common.h.  (The order of the launch_cfg uses below is the order hipcc instantiates the kernels in, and
+// their code depends on it.)
+int launch_prefill_main(const PrefillKernelParams &p, int dtype, int head_dim, bool causal, hipStream_t stream, int force) {
+    const bool prescaled = force == 0 ? p.fast_scale != 0 : force == 1;
+    if (prescaled) return launch_cfg<2, 6, 0>(p, dtype, head_dim, causal, stream);
+    if (force <= 2) return launch_cfg<2, 2, 0>(p, dtype, head_dim, causal, stream);     // prefetch distance 2, staged softmax
+#ifdef SFA_WITH_VARIANTS
+    if (force == 3) return launch_cfg<2, 0, 0>(p, dtype, head_dim, causal, stream);
+    if (force == 4) return launch_cfg<2, 2, 2>(p, dtype, head_dim, causal, stream);
 #endif
-    if (which == 3) return launch_cfg<2, 6, 0>(p, dtype, head_dim, causal, stream);     // prescaled Q, forced
-    if (which == 10) return launch_cfg<2, 2, 0>(p, dtype, head_dim, causal, stream);    // exact scale, forced
-    return fail(SFA_ERR_BAD_SHAPE, "prefill_impl %d needs the A/B build of the library (build_lib(variants=True))", which);
+    return fail(SFA_ERR_BAD_SHAPE, "launch_prefill_main: force %d", force);
 }
 
 }  // namespace sfa

@@ -305,7 +305,7 @@ int launch_t(const PrefillKernelParams &p_in, bool causal, int force, hipStream_
     PrefillKernelParams p = p_in;
     p.nq_tiles = (p.Sq + kBM2 - 1) / kBM2;              // 128-row q-tiles
     size_t lds = Lds<D, kBN2, 3, 2>::TOTAL;
-#ifdef SFA_WITH_VARIANTS      // diagnostic, the A/B library only: one workgroup (one wave per SIMD) per CU
+#ifdef SFA_WITH_VARIANTS      // diagnostic, the A/B library only (sfa_debug_set refuses it elsewhere): one workgroup per CU
     if (g_knobs.bm128_one_wg.load(std::memory_order_relaxed) > 0) {
         lds = 100 * 1024;
         static DynLdsAttr attr;

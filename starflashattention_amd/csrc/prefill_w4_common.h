@@ -28,12 +28,6 @@ __device__ __forceinline__ void mfma_qk_first(f32x16 &s, typename Tr::mfma_vec k
     else asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&v"(s) : "v"(k), "a"(q));
 }
 template <class Tr>
-__device__ __forceinline__ void mfma_qk_first_c(f32x16 &s, typename Tr::mfma_vec k, typename Tr::mfma_vec q, const f32x16 &c) {
-    // C operand = a VALU-written register tuple: two wait states in front (hazard (2))
-    if constexpr (Tr::id == 1) asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %3" : "=&v"(s) : "v"(k), "a"(q), "v"(c));
-    else asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_f16 %0, %1, %2, %3" : "=&v"(s) : "v"(k), "a"(q), "v"(c));
-}
-template <class Tr>
 __device__ __forceinline__ void mfma_qk(f32x16 &s, typename Tr::mfma_vec k, typename Tr::mfma_vec q) {
     if constexpr (Tr::id == 1) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(s) : "v"(k), "a"(q));
     else asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(s) : "v"(k), "a"(q));

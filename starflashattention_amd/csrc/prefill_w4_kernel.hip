@@ -3,7 +3,7 @@
 // full, MHA or GQA, any strides.  The reference has no prefill kernel; this is the kernel BASELINE.json's
 // headline metric is quoted on (SURVEY.md 8(a) A-new).
 //
-// Structure (unchanged from round 2, prefill_w4r2_kernel.hip -- kept in the A/B library):
+// Structure (unchanged from round 2's generation of this kernel):
 //   * workgroup = 4 waves = one 256-row q-tile; a wave owns 64 query rows = two 32-row query blocks, so every
 //     K / V fragment read from LDS feeds TWO MFMAs; one wave per SIMD with the whole 512-entry register file.
 //   * O^T (128 registers) and the Q^T fragments (64) live in the ACCUMULATOR half of the register file, by NAME
@@ -169,7 +169,7 @@ __device__ __forceinline__ void rescale_o(int q, float alpha) {
     asm volatile("s_nop 1" ::: SFA_AOWN);   // v_accvgpr_write -> the next MFMA that reads it as C: two wait states
 }
 
-// ---- the element pipeline (see prefill_w4r2_kernel.hip for the measurements behind it) ----------------------
+// ---- the element pipeline (measured on round 2's generation of this kernel: DESIGN.md) -----------------------
 // A half-step is 32 GAPS -- one MFMA each -- and the softmax of a half-tile is cut into per-ELEMENT stages:
 //     F  s = s * c2 - msc          (exact flavour only)
 //     X  s = exp2(s)
@@ -1263,7 +1263,7 @@ bool prefill_w4_serves(const PrefillKernelParams &p, int head_dim) {
            p.qs[2] * 2 < (1ll << 24);
 }
 
-// force: 0 = flavour by policy (exact unless the caller opted into fast_scale), 1 = prescaled, 2 = exact
+// force (prefill_common.h): 0 = flavour by policy, 1 = prescaled, 2 = exact; 3 / 4 = the q-tile stamping / event-log builds
 int launch_prefill_w4(const PrefillKernelParams &p, int dtype, int head_dim, bool causal, hipStream_t stream, int force) {
     if (dtype != SFA_DTYPE_FP16 && dtype != SFA_DTYPE_BF16)
         return fail(SFA_ERR_BAD_DTYPE, "sfa_prefill_fwd: dtype %d is not fp16(0)/bf16(1)", dtype);
@@ -1272,12 +1272,13 @@ int launch_prefill_w4(const PrefillKernelParams &p, int dtype, int head_dim, boo
     if (!prefill_w4_serves(p, head_dim))
         return fail(SFA_ERR_BAD_SHAPE, "sfa_prefill_fwd: one head's Q/K/V rows span more than 2 GiB");
     const bool prescaled = force == 0 ? p.fast_scale != 0 : force == 1;
-    (void)prescaled;
-#ifdef SFA_WITH_VARIANTS        // the q-tile stamping build (tools/w4_item_stamps.py): the A/B library only
-    if (force == 3) return launch_w4_t<Bf16, 128, 2, 256>(p, causal, stream);
-    if (force == 4) return launch_w4_t<Bf16, 128, 2, 1>(p, causal, stream);         // the event log (tools/w4_events.py)
+#ifdef SFA_WITH_VARIANTS        // the A/B library only
+    if (force == 3) return launch_w4_t<Bf16, 128, 2, 256>(p, causal, stream);      // q-tile stamps (tools/w4_seam_stamps.py)
+    if (force == 4) return launch_w4_t<Bf16, 128, 2, 1>(p, causal, stream);        // event log (tools/w4_events.py)
 #endif
 #ifdef SFA_W4_DEV       // development builds: one flavour, one dtype (seconds instead of minutes to compile)
+    if (dtype != SFA_DTYPE_BF16 || prescaled)
+        return fail(SFA_ERR_BAD_DTYPE, "sfa_prefill_fwd: this SFA_W4_DEV build of the 4-wave kernel serves bf16 exact scale only");
     return launch_w4_t<Bf16, 128, 2>(p, causal, stream);
 #else
     if (dtype == SFA_DTYPE_FP16)

@@ -64,11 +64,11 @@ int check_launch(const char *what);
 // Test / A-B knobs, set through sfa_debug_set() (include/star_flash_attn.h) and nothing else: the launch
 // paths read no environment variable.  -1 = the library's own choice.
 struct DebugKnobs {
-    std::atomic<int> prefill_impl{-1};      // prefill_dispatch.hip: which prefill kernel generation
+    std::atomic<int> prefill_impl{-1};      // prefill_dispatch.hip: which prefill kernel (PrefillImpl, prefill_common.h)
     std::atomic<int> prefill_pairs{-1};     // prefill_kernel.hip: balanced q-tile pairs per workgroup (1 or 2)
     std::atomic<int> decode_nt{-1};         // decode kernels: 0 / 1 force default / non-temporal cache loads
     std::atomic<int> decode_gqa_mfma{-1};   // decode_gqa_kernel.hip: 0 forces the VALU grouped-query kernel
-    std::atomic<int> bm128_one_wg{-1};      // prefill_kernel_bm128.hip: 1 = one workgroup per CU (diagnostic)
+    std::atomic<int> bm128_one_wg{-1};      // prefill_kernel_bm128.hip: 1 = one workgroup per CU (A/B library only)
     std::atomic<int> last_prefill_kernel{-1};   // written by launch_prefill: what ran last (sfa_debug_get)
 };
 extern DebugKnobs g_knobs;

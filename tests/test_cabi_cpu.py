@@ -6,6 +6,7 @@ import os
 import re
 
 import pytest
+import torch
 
 from conftest import ROOT
 from starflashattention_amd import _lib
@@ -92,6 +93,35 @@ def test_argument_validation_without_gpu(lib):
     assert lib.sfa_debug_set(b"prefill_impl", 40) == 0 and lib.sfa_debug_set(b"prefill_impl", -1) == 0
     assert lib.sfa_debug_set(b"no_such_knob", 1) == -2 and b"unknown knob" in lib.sfa_last_error()
     assert lib.sfa_debug_set(None, 1) == -1
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason="calls sfa_prefill_fwd with fake device pointers")
+def test_prefill_impl_rejects_unknown_ids(lib):
+    """prefill_impl ids outside the table of prefill_common.h (the retired generations' 0, 30, 84 among them) and the
+    diagnostic builds this library was not compiled with (43, 44) fail before any HIP call."""
+    lib.sfa_debug_get.restype = ctypes.c_int
+    p = _lib.PrefillArgs()
+    p.q, p.k, p.v, p.o = 0x1000, 0x2000, 0x3000, 0x4000
+    p.batch, p.heads_q, p.heads_kv, p.seqlen_q, p.seqlen_k, p.head_dim = 1, 1, 1, 1, 1, 128
+    for st in (p.q_stride, p.k_stride, p.v_stride, p.o_stride):
+        st[0], st[1], st[2] = 128, 128, 128
+    p.dtype = _lib.DTYPE_BF16
+    last = lib.sfa_debug_get(b"last_prefill_kernel")
+    try:
+        for impl in (0, 30, 43, 44, 84, 5, 999):
+            assert lib.sfa_debug_set(b"prefill_impl", impl) == 0
+            for head_dim in (128, 256):             # head_dim 256 ignores the ids of the table, not unknown ones
+                p.head_dim = head_dim
+                assert lib.sfa_prefill_fwd(ctypes.byref(p), None) == -2, (impl, head_dim)
+                err = lib.sfa_last_error()
+                assert b"prefill_impl %d" % impl in err, err
+                assert (b"diagnostics build" in err) == (impl in (43, 44)), err
+        assert lib.sfa_debug_get(b"last_prefill_kernel") == last          # nothing was launched
+        assert lib.sfa_debug_set(b"bm128_one_wg", 1) == -2 and b"diagnostics build" in lib.sfa_last_error()
+        assert lib.sfa_debug_set(b"bm128_one_wg", 0) == 0
+    finally:
+        for knob in (b"prefill_impl", b"bm128_one_wg"):
+            lib.sfa_debug_set(knob, -1)
 
 
 def test_launch_paths_read_no_environment():

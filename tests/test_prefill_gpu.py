@@ -76,7 +76,7 @@ CASES = [  # B, Hq, Hkv, Sq, Sk, D
 # every kernel the dispatcher can pick must pass on its own: the 4-wave persistent kernel (head_dim 128
 # and 256), the 8-wave 256-row pipelined kernel (one or two q-tile pairs per workgroup) and the 128-row
 # geometry for small grids, each in its exact-scale and its prescaled-Q flavour, and the auto choice.
-# The earlier generations (baseline, 16x16x32 MFMA) live in the A/B build only: tests/test_variants_gpu.py.
+# (The diagnostic builds of the A/B library -- prefill_impl 2, 4, 43, 44 -- are tools, not tested kernels.)
 IMPLS = {"auto": -1, "w4": 42, "prescaled_w4": 41, "rows256": 10, "rows256x2": 10, "rows128": 22,
          "prescaled256": 3, "prescaled256x2": 3, "prescaled128": 21, "d256_fallback": 61}
 W4_DIMS = (128,)            # head dims the 4-wave kernel serves

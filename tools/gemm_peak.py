@@ -2,7 +2,7 @@
 """Calibration: what the matrix cores of THIS device sustain on a plain library GEMM (hipBLASLt through torch.matmul),
 bf16, with the operand data the attention benchmark uses (randn) and with all-zero operands.  The difference is the
 power cap: MI355X clocks down under dense MFMA work on real data (the 4-wave prefill kernel measures 1.79-1.83 GHz
-against 2.4 GHz nominal with s_memtime / s_memrealtime, tools/w4_item_stamps.py)."""
+against 2.4 GHz nominal with s_memtime / s_memrealtime, tools/w4_seam_stamps.py)."""
 import sys, torch
 dev = torch.device("cuda:0")
 def bench(a, b, n=20):

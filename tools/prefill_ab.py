@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """In-process A/B of the prefill kernels at the headline shape (interleaved rounds; impl numbers:
 prefill_dispatch.hip -- -1 auto, 1 8-wave (exact scale), 3 prescaled Q, 10 exact forced, 20-22 128-row,
-40-42 the 4-wave persistent kernel; 0 baseline and 30-32 16x16x32 need the A/B library:
+40-42 the 4-wave persistent kernel; the diagnostic build 2 (un-staged softmax) needs the A/B library:
 SFA_LIB_PATH=starflashattention_amd/lib/libStarFlashAttention_ab.so;
 cdna_hip_programming.md rule 24).  usage: python tools/prefill_ab.py [impl ...] [--noncausal] [--d64 | --d256]"""
 import os, sys, time

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Diagnostic: per-wave cycle shares of one workgroup's steps 8..15 (prefill_impl 4: the stamping build of the 8-wave kernel).
-Stamps: 0 start of H1, 1 end of H1 (before barrier), 2 after barrier, 3 end of H2."""
+"""Diagnostic: per-wave cycle shares of one workgroup's steps 8..15 (prefill_impl 4: the stamping build of the 8-wave kernel, A/B library only).
+Stamps: 0 start of H1, 1 end of H1 (before barrier), 2 after barrier, 3 end of H2.
+usage: SFA_LIB_PATH=.../libStarFlashAttention_ab.so python tools/prefill_stamps.py [--noncausal]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Diagnostic (prefill_impl 4: the stamping build of the 8-wave kernel): where a workgroup's life goes.  Stamps: 0 workgroup start,
+"""Diagnostic (prefill_impl 4: the stamping build of the 8-wave kernel, A/B library only, SFA_LIB_PATH): where a workgroup's life goes.  Stamps: 0 workgroup start,
 1 first q-tile's loop entry (end of the staging prologue), 2 end of the first q-tile's loop, 3 end of
 the workgroup (second q-tile of the pair included).  usage: [--noncausal] [--shape=B,H,S]"""
 import os, sys
