@@ -19,6 +19,7 @@
  *   sfa_compute_rotary_table    <- compute_rotary_table<T>   src/flash_attn.h:9-10, cu:512-538
  *   sfa_fill_16bit              <- init_half_array           src/flash_attn.h:11,   cu:493-510
  *   sfa_prefill_fwd             <- (no reference function; BASELINE.json configs 2,3,5)
+ *   sfa_decode_chunk            <- (no reference function: prompt ingestion before the first decode step)
  * The Python-facing mha_fwd_cuda (src/flash_api.cpp:42-68) and the C++ template
  * surface (src/flash_attn.h) in this repo are thin layers over these symbols.
  */
@@ -36,7 +37,9 @@ extern "C" {
  *   2  kv_layout, fast_scale
  *   3  page_size / block_table / block_table_stride / num_pages / num_heads_kv appended to sfa_decode_args;
  *      a block_table entry outside the pool on the APPEND page now rejects the sequence; sfa_debug_set
- *   4  sfa_debug_get, sfa_decode_workspace_bytes_gqa added (nothing changed) */
+ *   4  sfa_debug_get, sfa_decode_workspace_bytes_gqa added (nothing changed); sfa_decode_chunk and
+ *      sfa_decode_chunk_workspace_bytes added later under the same version, with no layout or meaning change:
+ *      callers detect them by symbol */
 #define SFA_ABI_VERSION 4
 
 typedef enum sfa_status {
@@ -165,6 +168,34 @@ int sfa_decode_reset_status(void *workspace, void *stream);
  * SFA_ERR_BLOCK_TABLE_RANGE. */
 int sfa_decode_poll_status(const void *workspace, void *stream);
 int sfa_decode(const sfa_decode_args *args, void *stream);
+
+/* ---- decode chunk: n new tokens per sequence in one call ------------------------- */
+/*
+ * Exactly n successive sfa_decode calls, for every b, h and t in [0, n):
+ *   pos   = seq_len[b]                     NOT incremented (caller's job, as in sfa_decode)
+ *   q,k,v = qkv[b, t, ...] (+ bias)        same head split as sfa_decode, grouped queries included
+ *   q,k   = rope(q, k; pos + t)            sfa_decode's recipe (LUT row pos + t when tables are given)
+ *   cache[b, idx_layer, pos + t] = k, v    every kv_layout
+ *   o[b, t, h, :] = softmax(q . K[0 .. pos+t]^T * scale) . V[0 .. pos+t]      (fp32 accumulate)
+ * so token t sees the history and the new tokens 0..t (causal within the chunk).
+ * qkv is [batch, n, 3, num_heads, head_dim] (grouped: [batch, n, H + 2*Hkv, head_dim]); args->stride = elements
+ * between batches (0 => n * qkv_token_stride), qkv_token_stride = elements between tokens (0 => (H + 2*Hkv) *
+ * head_dim); args->o is [batch, n, num_heads, head_dim], contiguous.  Every other field of sfa_decode_args keeps its
+ * sfa_decode meaning; head_dim 64 or 128 (256 returns SFA_ERR_UNSUPPORTED_HEAD_DIM).  num_tokens = 0 does nothing.
+ * Ragged prompts: pad every sequence to a common n.  The rows written past a sequence's real length land at
+ * positions >= its next seq_len, so the following decode steps overwrite them before anything reads them, and
+ * causality keeps the real tokens' outputs independent of the padding.  With a paged cache the table must map the
+ * padded rows [pos, pos + n) to valid pages too.
+ * Rejection, with the status word of sfa_decode (sfa_decode_poll_status): pos < 0 or pos + n > memory_max_len, or
+ * (paged) a page covering [pos, pos + n) outside [0, num_pages), leaves sequence b's cache untouched, makes o[b] NaN
+ * and raises SFA_ERR_SEQ_LEN_RANGE / SFA_ERR_BLOCK_TABLE_RANGE.  A bad entry on a page that is only read is not
+ * dereferenced; it raises SFA_ERR_BLOCK_TABLE_RANGE and turns the outputs that may depend on it into NaN.
+ * Workspace: the 256-byte status block, the rotated Q, then (split key range) fp32 partials;
+ * sfa_decode_chunk_workspace_bytes sizes it (num_splits <= 0: the library's choice for this shape).
+ */
+int    sfa_decode_chunk(const sfa_decode_args *args, int num_tokens, int64_t qkv_token_stride, void *stream);
+size_t sfa_decode_chunk_workspace_bytes(int batch_size, int num_heads, int num_heads_kv, int head_dim,
+                                        int memory_max_len, int num_tokens, int num_splits);
 
 /* ---- prefill: O = softmax(mask(Q K^T * scale)) V ------------------------------- */
 /*

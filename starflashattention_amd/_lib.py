@@ -22,6 +22,7 @@ EXPORTED_SYMBOLS = [
     "sfa_decode_workspace_bytes", "sfa_decode_workspace_bytes_gqa", "sfa_decode_auto_splits", "sfa_decode_reset_status",
     "sfa_decode_poll_status", "sfa_decode", "sfa_prefill_fwd",
     "sfa_compute_rotary_table", "sfa_fill_16bit", "sfa_debug_set", "sfa_debug_get",
+    "sfa_decode_chunk", "sfa_decode_chunk_workspace_bytes",
 ]
 
 
@@ -96,6 +97,10 @@ def load():
     lib.sfa_decode_poll_status.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     lib.sfa_decode.restype = ctypes.c_int
     lib.sfa_decode.argtypes = [ctypes.POINTER(DecodeArgs), ctypes.c_void_p]
+    lib.sfa_decode_chunk.restype = ctypes.c_int
+    lib.sfa_decode_chunk.argtypes = [ctypes.POINTER(DecodeArgs), ctypes.c_int, ctypes.c_int64, ctypes.c_void_p]
+    lib.sfa_decode_chunk_workspace_bytes.restype = ctypes.c_size_t
+    lib.sfa_decode_chunk_workspace_bytes.argtypes = [ctypes.c_int] * 7
     lib.sfa_prefill_fwd.restype = ctypes.c_int
     lib.sfa_prefill_fwd.argtypes = [ctypes.POINTER(PrefillArgs), ctypes.c_void_p]
     lib.sfa_compute_rotary_table.restype = ctypes.c_int

@@ -58,6 +58,67 @@ static int auto_splits(int B, int H, int /*D*/, int M) {
     return (int)s;
 }
 
+// The kernel parameters of an (already validated) sfa_decode_args, shared by sfa_decode and sfa_decode_chunk; the
+// callers place part_o / part_ml in the workspace.
+static DecodeKernelParams decode_params(const sfa_decode_args *a, int hkv, int page_shift, int S, long long stride) {
+    const long long hd = (long long)hkv * a->head_dim;          // elements per cache row
+    DecodeKernelParams p;
+    memset(&p, 0, sizeof(p));
+    p.qkv = (const uint16_t *)a->qkv;
+    p.q_bias = (const uint16_t *)a->q_bias;
+    p.k_bias = (const uint16_t *)a->k_bias;
+    p.v_bias = (const uint16_t *)a->v_bias;
+    p.o = (uint16_t *)a->o;
+    p.seq_len = (const int32_t *)a->seq_len;
+    p.k_cache = (uint16_t *)a->k_cache_table;
+    p.v_cache = (uint16_t *)a->v_cache_table;
+    p.cos_tab = (const uint16_t *)a->rotary_cos_table;
+    p.sin_tab = (const uint16_t *)a->rotary_sin_table;
+    p.status = (int32_t *)a->workspace;
+    p.B = a->batch_size;
+    p.M = a->memory_max_len;
+    p.H = a->num_heads;
+    p.Hkv = hkv;
+    p.L = a->num_layer;
+    p.layer = a->idx_layer;
+    p.rot_dim = a->rotary_embedding_dim;
+    p.num_splits = S;
+    p.qkv_stride = stride;
+    if (a->kv_layout == SFA_KV_PAGED) {
+        p.kv_row_stride = hd;                   // rows of a page are [page_size, H, D]
+        p.kv_head_stride = a->head_dim;
+        p.block_table = (const int32_t *)a->block_table;
+        p.page_shift = page_shift;
+        p.table_stride = a->block_table_stride;
+        p.num_pages = a->num_pages;
+        p.page_stride = (long long)a->num_layer * a->page_size * hd;
+    } else if (a->kv_layout == SFA_KV_BLHMD) {
+        p.kv_row_stride = a->head_dim;
+        p.kv_head_stride = (long long)a->memory_max_len * a->head_dim;
+    } else {
+        p.kv_row_stride = hd;
+        p.kv_head_stride = a->head_dim;
+    }
+    const float scale = a->head_dim_inv > 0.f ? a->head_dim_inv : 1.0f / std::sqrt((float)a->head_dim);
+    p.scale_log2 = scale * 1.4426950408889634f;
+    return p;
+}
+
+// Split count of sfa_decode_chunk for num_splits <= 0.  The attention kernel runs one 8-wave workgroup per (batch, kv
+// head, 256-row q-tile, split), one per CU (its LDS): split the key range only while B * Hkv * q-tiles leaves CUs
+// idle, aim for ~256 workgroups, keep every split at least 512 cache rows (8 tiles) of memory_max_len long and at
+// most 32 splits.  The split count is chosen on the host from memory_max_len; the device splits the actual
+// seq_len[b] + n keys, so a split past a sequence's keys only writes an empty partial.
+static int chunk_auto_splits(int B, int Hkv, int rows, int M) {
+    const long long wgs = (long long)B * Hkv * ((rows + 255) / 256);
+    long long s = (256 + wgs - 1) / wgs;
+    const long long cap = M / 512 > 1 ? M / 512 : 1;
+    if (s > cap) s = cap;
+    if (s > 32) s = 32;
+    if (s < 1) s = 1;
+    return (int)s;
+}
+
 }  // namespace sfa
 
 using namespace sfa;
@@ -184,7 +245,6 @@ int sfa_decode(const sfa_decode_args *a, void *stream) {
         (group != 1 && group != 2 && group != 4 && group != 8 && group != 16))
         return fail(SFA_ERR_BAD_SHAPE, "sfa_decode: num_heads=%d / num_heads_kv=%d must be 1, 2, 4, 8 or 16",
                     a->num_heads, a->num_heads_kv);
-    const long long hd = (long long)hkv * a->head_dim;          // elements per cache row
     const long long row = (long long)(a->num_heads + 2 * hkv) * a->head_dim;    // packed q,k,v of one token
     const long long stride = a->stride > 0 ? a->stride : row;
     if (stride < row || (stride % 8) != 0)
@@ -233,50 +293,127 @@ int sfa_decode(const sfa_decode_args *a, void *stream) {
     if ((uintptr_t)a->workspace & 255)
         return fail(SFA_ERR_BAD_SHAPE, "sfa_decode: workspace must be 256-byte aligned");
 
-    DecodeKernelParams p;
-    memset(&p, 0, sizeof(p));
-    p.qkv = (const uint16_t *)a->qkv;
-    p.q_bias = (const uint16_t *)a->q_bias;
-    p.k_bias = (const uint16_t *)a->k_bias;
-    p.v_bias = (const uint16_t *)a->v_bias;
-    p.o = (uint16_t *)a->o;
-    p.seq_len = (const int32_t *)a->seq_len;
-    p.k_cache = (uint16_t *)a->k_cache_table;
-    p.v_cache = (uint16_t *)a->v_cache_table;
-    p.cos_tab = (const uint16_t *)a->rotary_cos_table;
-    p.sin_tab = (const uint16_t *)a->rotary_sin_table;
+    DecodeKernelParams p = decode_params(a, hkv, page_shift, S, stride);
     char *ws = (char *)a->workspace;
-    p.status = (int32_t *)ws;
     const size_t bhs = (size_t)a->batch_size * a->num_heads * S;
     p.part_o = (float *)(ws + kStatusBytes);
     p.part_ml = (float2 *)(ws + kStatusBytes + align_up(bhs * a->head_dim * sizeof(float), 256));
-    p.B = a->batch_size;
-    p.M = a->memory_max_len;
-    p.H = a->num_heads;
-    p.Hkv = hkv;
-    p.L = a->num_layer;
-    p.layer = a->idx_layer;
-    p.rot_dim = a->rotary_embedding_dim;
-    p.num_splits = S;
-    p.qkv_stride = stride;
-    if (a->kv_layout == SFA_KV_PAGED) {
-        p.kv_row_stride = hd;                   // rows of a page are [page_size, H, D]
-        p.kv_head_stride = a->head_dim;
-        p.block_table = (const int32_t *)a->block_table;
-        p.page_shift = page_shift;
-        p.table_stride = a->block_table_stride;
-        p.num_pages = a->num_pages;
-        p.page_stride = (long long)a->num_layer * a->page_size * hd;
-    } else if (a->kv_layout == SFA_KV_BLHMD) {
-        p.kv_row_stride = a->head_dim;
-        p.kv_head_stride = (long long)a->memory_max_len * a->head_dim;
-    } else {
-        p.kv_row_stride = hd;
-        p.kv_head_stride = a->head_dim;
-    }
-    const float scale = a->head_dim_inv > 0.f ? a->head_dim_inv : 1.0f / std::sqrt((float)a->head_dim);
-    p.scale_log2 = scale * 1.4426950408889634f;
     return launch_decode(p, a->dtype, a->head_dim, (hipStream_t)stream);
+}
+
+size_t sfa_decode_chunk_workspace_bytes(int batch_size, int num_heads, int num_heads_kv, int head_dim,
+                                        int memory_max_len, int num_tokens, int num_splits) {
+    if (batch_size <= 0 || num_heads <= 0 || head_dim <= 0 || num_tokens <= 0) return kStatusBytes;
+    const int hkv = num_heads_kv > 0 ? num_heads_kv : num_heads;
+    const long long rows = (long long)num_tokens * (num_heads / hkv);     // query rows per (batch, kv head)
+    const int S = num_splits > 0 ? num_splits
+                                 : chunk_auto_splits(batch_size, hkv, (int)(rows < INT_MAX ? rows : INT_MAX), memory_max_len);
+    const size_t bhr = (size_t)batch_size * hkv * rows;
+    size_t bytes = kStatusBytes + align_up(bhr * head_dim * sizeof(uint16_t), 256);     // rotated Q
+    if (S > 1) {
+        bytes += align_up(bhr * S * head_dim * sizeof(float), 256);
+        bytes += align_up(bhr * S * sizeof(float2), 256);
+    }
+    return bytes;
+}
+
+int sfa_decode_chunk(const sfa_decode_args *a, int num_tokens, int64_t qkv_token_stride, void *stream) {
+    if (!a) return fail(SFA_ERR_NULL_POINTER, "sfa_decode_chunk: args is NULL");
+    if (!a->qkv || !a->o || !a->seq_len || !a->k_cache_table || !a->v_cache_table)
+        return fail(SFA_ERR_NULL_POINTER, "sfa_decode_chunk: qkv/o/seq_len/k_cache_table/v_cache_table must be non-NULL");
+    if ((a->rotary_cos_table == nullptr) != (a->rotary_sin_table == nullptr))
+        return fail(SFA_ERR_NULL_POINTER, "sfa_decode_chunk: give both rotary tables or neither");
+    if (num_tokens < 0) return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk: num_tokens=%d < 0", num_tokens);
+    if (a->batch_size < 0 || a->batch_size > 65535 || a->num_heads <= 0 || a->memory_max_len <= 0 || a->num_layer <= 0)
+        return fail(SFA_ERR_BAD_SHAPE,
+                    "sfa_decode_chunk: batch_size=%d (<= 65535) num_heads=%d memory_max_len=%d num_layer=%d",
+                    a->batch_size, a->num_heads, a->memory_max_len, a->num_layer);
+    if (a->idx_layer < 0 || a->idx_layer >= a->num_layer)
+        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk: idx_layer=%d outside [0, num_layer=%d)", a->idx_layer,
+                    a->num_layer);
+    if (a->head_dim == 256)
+        return fail(SFA_ERR_UNSUPPORTED_HEAD_DIM,
+                    "sfa_decode_chunk: head_dim 256 is not supported by the chunk path yet (64 or 128; sfa_decode "
+                    "serves 256 one token at a time)");
+    if (a->head_dim != 64 && a->head_dim != 128)
+        return fail(SFA_ERR_UNSUPPORTED_HEAD_DIM, "sfa_decode_chunk: head_dim %d not in {64, 128}", a->head_dim);
+    if (a->rotary_embedding_dim < 0 || a->rotary_embedding_dim > a->head_dim || (a->rotary_embedding_dim & 1))
+        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk: rotary_embedding_dim=%d must be even and in [0, head_dim]",
+                    a->rotary_embedding_dim);
+    if (a->dtype != SFA_DTYPE_FP16 && a->dtype != SFA_DTYPE_BF16)
+        return fail(SFA_ERR_BAD_DTYPE, "sfa_decode_chunk: dtype %d is not fp16(0)/bf16(1)", a->dtype);
+    const int hkv = a->num_heads_kv > 0 ? a->num_heads_kv : a->num_heads;
+    const int group = hkv > 0 ? a->num_heads / hkv : 0;
+    if (a->num_heads_kv < 0 || group * hkv != a->num_heads ||
+        (group != 1 && group != 2 && group != 4 && group != 8 && group != 16))
+        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk: num_heads=%d / num_heads_kv=%d must be 1, 2, 4, 8 or 16",
+                    a->num_heads, a->num_heads_kv);
+    const long long row = (long long)(a->num_heads + 2 * hkv) * a->head_dim;    // packed q,k,v of one token
+    const long long tok = qkv_token_stride > 0 ? qkv_token_stride : row;
+    if (tok < row || (tok % 8) != 0)
+        return fail(SFA_ERR_BAD_SHAPE,
+                    "sfa_decode_chunk: qkv_token_stride %lld must be >= (H + 2*Hkv)*D and a multiple of 8", tok);
+    const long long stride = a->stride > 0 ? a->stride : (long long)num_tokens * tok;
+    if ((num_tokens > 0 && stride < (num_tokens - 1) * tok + row) || (stride % 8) != 0)
+        return fail(SFA_ERR_BAD_SHAPE,
+                    "sfa_decode_chunk: qkv stride %lld must be >= (num_tokens-1)*token_stride + (H + 2*Hkv)*D and a "
+                    "multiple of 8", stride);
+    if ((long long)num_tokens * group > INT_MAX)
+        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk: num_tokens * group = %lld query rows per kv head is too many",
+                    (long long)num_tokens * group);
+    if (a->num_splits > 1024)
+        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk: num_splits=%d > 1024", a->num_splits);
+    if (a->kv_layout != SFA_KV_BLMHD && a->kv_layout != SFA_KV_BLHMD && a->kv_layout != SFA_KV_PAGED)
+        return fail(SFA_ERR_BAD_SHAPE,
+                    "sfa_decode_chunk: kv_layout %d is not SFA_KV_BLMHD(0)/SFA_KV_BLHMD(1)/SFA_KV_PAGED(2)", a->kv_layout);
+    // the attention kernel addresses the 64 rows of a tile with 32-bit lane offsets
+    if (a->kv_layout != SFA_KV_BLHMD && 128ll * hkv * a->head_dim >= (1ll << 31))
+        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk: num_heads_kv * head_dim = %lld too large",
+                    (long long)hkv * a->head_dim);
+    int page_shift = 0;
+    if (a->kv_layout == SFA_KV_PAGED) {
+        if (!a->block_table) return fail(SFA_ERR_NULL_POINTER, "sfa_decode_chunk: kv_layout PAGED needs block_table");
+        if (a->page_size < 16 || (a->page_size & (a->page_size - 1)))
+            return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk: page_size=%d must be a power of two >= 16", a->page_size);
+        while ((1 << page_shift) < a->page_size) ++page_shift;
+        if (a->num_pages <= 0 || (long long)a->block_table_stride * a->page_size < (long long)a->memory_max_len)
+            return fail(SFA_ERR_BAD_SHAPE,
+                        "sfa_decode_chunk: num_pages=%d, block_table_stride=%d * page_size=%d must cover memory_max_len=%d",
+                        a->num_pages, a->block_table_stride, a->page_size, a->memory_max_len);
+        if ((uintptr_t)a->block_table & 3)
+            return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk: block_table must be 4-byte aligned");
+    }
+    const uintptr_t align_or = (uintptr_t)a->qkv | (uintptr_t)a->o | (uintptr_t)a->k_cache_table |
+                               (uintptr_t)a->v_cache_table | (uintptr_t)a->q_bias | (uintptr_t)a->k_bias |
+                               (uintptr_t)a->v_bias;
+    if (align_or & 15) return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk: tensors must be 16-byte aligned");
+    if (a->batch_size == 0 || num_tokens == 0) return SFA_OK;
+
+    const int rows = num_tokens * group;
+    const int S = a->num_splits > 0 ? a->num_splits : chunk_auto_splits(a->batch_size, hkv, rows, a->memory_max_len);
+    const size_t need = sfa_decode_chunk_workspace_bytes(a->batch_size, a->num_heads, hkv, a->head_dim,
+                                                         a->memory_max_len, num_tokens, S);
+    if (!a->workspace) return fail(SFA_ERR_NULL_POINTER, "sfa_decode_chunk: workspace is NULL (need %zu bytes)", need);
+    if (a->workspace_bytes < need)
+        return fail(SFA_ERR_WORKSPACE_TOO_SMALL, "sfa_decode_chunk: workspace has %zu bytes, need %zu",
+                    a->workspace_bytes, need);
+    if ((uintptr_t)a->workspace & 255)
+        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk: workspace must be 256-byte aligned");
+
+    ChunkKernelParams p;
+    memset(&p, 0, sizeof(p));
+    p.d = decode_params(a, hkv, page_shift, S, stride);
+    char *ws = (char *)a->workspace;
+    const size_t bhr = (size_t)a->batch_size * hkv * rows;
+    const size_t q_bytes = align_up(bhr * a->head_dim * sizeof(uint16_t), 256);
+    p.q_rot = (uint16_t *)(ws + kStatusBytes);
+    p.d.part_o = (float *)(ws + kStatusBytes + q_bytes);
+    p.d.part_ml = (float2 *)(ws + kStatusBytes + q_bytes + align_up(bhr * S * a->head_dim * sizeof(float), 256));
+    p.tok_stride = tok;
+    p.n = num_tokens;
+    p.G = group;
+    p.R = rows;
+    return launch_decode_chunk(p, a->dtype, a->head_dim, (hipStream_t)stream);
 }
 
 int sfa_prefill_fwd(const sfa_prefill_args *a, void *stream) {

@@ -38,6 +38,18 @@ struct DecodeKernelParams {
     float scale_log2;       // softmax scale * log2(e)
 };
 
+// sfa_decode_chunk (decode_chunk_kernel.hip): n new tokens per sequence.  Workspace: [0,256) status block,
+// then the rotated Q [B, Hkv, R, D] (16 bit, row r = t*G + g of kv head hk is query head hk*G + g of token t),
+// then (num_splits > 1) fp32 partial outputs [B, Hkv, S, R, D] and float2 (m, l) [B, Hkv, S, R].
+struct ChunkKernelParams {
+    DecodeKernelParams d;   // every field keeps its sfa_decode meaning; d.part_o / d.part_ml are the chunk partials
+    uint16_t *q_rot;        // workspace: rotated, rounded Q
+    long long tok_stride;   // elements between tokens of qkv
+    int n;                  // new tokens per sequence
+    int G;                  // query heads per kv head
+    int R;                  // query rows per (batch, kv head) = n * G
+};
+
 struct PrefillKernelParams {
     const uint16_t *q, *k, *v;
     uint16_t *o;
@@ -54,6 +66,7 @@ struct PrefillKernelParams {
 int launch_decode(const DecodeKernelParams &p, int dtype, int head_dim, hipStream_t stream);
 int launch_decode_gqa(const DecodeKernelParams &p, int dtype, int head_dim, hipStream_t stream);
 int launch_decode_gqa_mfma(const DecodeKernelParams &p, int dtype, int head_dim, hipStream_t stream);
+int launch_decode_chunk(const ChunkKernelParams &p, int dtype, int head_dim, hipStream_t stream);
 int launch_prefill(const PrefillKernelParams &p, int dtype, int head_dim, bool causal, hipStream_t stream);
 int launch_prefill_no_keys(const PrefillKernelParams &p, int head_dim, hipStream_t stream);
 int launch_rotary_table(void *cos_t, void *sin_t, int max_seq_len, int rot_dim, int dtype, hipStream_t stream);

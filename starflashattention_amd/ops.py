@@ -1,12 +1,14 @@
 """Host-side operators over the C ABI: torch tensors in, HIP kernels underneath.
 
 torch is plumbing here (device memory, current stream); every byte of compute happens in
-libStarFlashAttention.so.  The two public operators:
+libStarFlashAttention.so.  The public operators:
 
   flash_decode(...)   same arguments, meaning and side effects as the reference's
                       star_flash_attn.mha_fwd_cuda (src/flash_api.cpp:42-68): mutates `o` and the
                       two caches in place and returns `o`.
   flash_attn_fwd(...) prefill forward (new entry point; the reference is decode-only).
+  flash_decode_chunk(...)  n new tokens per sequence in one call: prompt ingestion, chunked prefill,
+                      speculative verification (new entry point).
 """
 import ctypes
 import math
@@ -69,26 +71,21 @@ def release_workspaces():
     _workspaces.clear()
 
 
-def flash_decode(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o,
-                 batch_size, memory_max_len, num_heads, head_dim, rotary_embedding_dim,
-                 max_input_length, num_layer, idx_layer, *, num_splits=0, _sized_by_query_heads=False,
-                 rotary_cos_table=None, rotary_sin_table=None, softmax_scale=None, kv_layout="blmhd",
-                 block_table=None, num_heads_kv=None):
-    """One decode step (see include/star_flash_attn.h, sfa_decode).  Returns `o` (same tensor).
-    kv_layout: "blmhd" = the reference's [B, L, M, H, D] caches; "blhmd" = head-major [B, L, H, M, D];
-    "paged" = page pools [num_pages, L, page_size, H, D] addressed through block_table (int32
-    [B, pages_per_seq]); memory_max_len is then the capacity of one sequence.
-    num_heads_kv (grouped queries, an extension): qkv is then [B, num_heads + 2*num_heads_kv, D] (q heads,
-    k heads, v heads), k_bias / v_bias and the caches carry num_heads_kv heads."""
-    lib = _lib.load()
+def _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size, memory_max_len,
+                 num_heads, head_dim, rotary_embedding_dim, max_input_length, num_layer, idx_layer, rotary_cos_table,
+                 rotary_sin_table, softmax_scale, kv_layout, block_table, num_heads_kv, tokens=None):
+    """Check the tensors of one decode call and fill its sfa_decode_args, all but the workspace, num_splits and stride.
+    tokens None: flash_decode (qkv [B, 3, H, D] or [B, H + 2*Hkv, D], o [B, H, D]); tokens = n: flash_decode_chunk
+    (qkv [B, n, 3, H, D] or [B, n, H + 2*Hkv, D], o [B, n, H, D]).  Returns (args, B, H, Hkv, D, M)."""
     _require(isinstance(qkv, torch.Tensor) and qkv.dtype in _DTYPES,
              f"qkv must be a float16 or bfloat16 tensor (got {getattr(qkv, 'dtype', type(qkv))})")
     dt, dev = qkv.dtype, qkv.device
     B, H, D, M, L = int(batch_size), int(num_heads), int(head_dim), int(memory_max_len), int(num_layer)
     Hkv = H if num_heads_kv is None else int(num_heads_kv)
     _require(Hkv > 0 and H % Hkv == 0, f"num_heads={H} must be a multiple of num_heads_kv={Hkv}")
-    _check_gpu_tensor(qkv, "qkv", dt, (B, 3, H, D) if Hkv == H else (B, H + 2 * Hkv, D))
-    _check_gpu_tensor(o, "o", dt, (B, H, D), dev)
+    lead = (B,) if tokens is None else (B, tokens)
+    _check_gpu_tensor(qkv, "qkv", dt, lead + ((3, H, D) if Hkv == H else (H + 2 * Hkv, D)))
+    _check_gpu_tensor(o, "o", dt, lead + (H, D), dev)
     _check_gpu_tensor(seq_len, "seq_len", torch.int32, (B,), dev)
     _require(kv_layout in _lib.KV_LAYOUTS, f"kv_layout must be one of {sorted(_lib.KV_LAYOUTS)} (got {kv_layout!r})")
     if kv_layout == "paged":
@@ -114,6 +111,47 @@ def flash_decode(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_
     for name, t in (("rotary_cos_table", rotary_cos_table), ("rotary_sin_table", rotary_sin_table)):
         if t is not None:
             _check_gpu_tensor(t, name, dt, (M, int(rotary_embedding_dim) // 2), dev)
+    a = _lib.DecodeArgs()
+    a.qkv = qkv.data_ptr()
+    a.q_bias, a.k_bias, a.v_bias = (b.data_ptr() if b is not None else None for b in biases)
+    a.o = o.data_ptr()
+    a.seq_len = seq_len.data_ptr()
+    a.k_cache_table = k_cache_table.data_ptr()
+    a.v_cache_table = v_cache_table.data_ptr()
+    a.rotary_cos_table = rotary_cos_table.data_ptr() if rotary_cos_table is not None else None
+    a.rotary_sin_table = rotary_sin_table.data_ptr() if rotary_sin_table is not None else None
+    a.batch_size, a.memory_max_len, a.num_heads, a.head_dim = B, M, H, D
+    a.head_dim_inv = float(softmax_scale) if softmax_scale else 1.0 / math.sqrt(D)
+    a.rotary_embedding_dim = int(rotary_embedding_dim)
+    a.max_input_length = int(max_input_length)
+    a.num_heads_kv = Hkv
+    a.num_layer, a.idx_layer = L, int(idx_layer)
+    a.dtype = _DTYPES[dt]
+    a.kv_layout = _lib.KV_LAYOUTS[kv_layout]
+    if kv_layout == "paged":
+        a.page_size, a.num_pages = page_size, num_pages
+        a.block_table = block_table.data_ptr()
+        a.block_table_stride = int(block_table.shape[1])
+    return a, B, H, Hkv, D, M
+
+
+def flash_decode(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o,
+                 batch_size, memory_max_len, num_heads, head_dim, rotary_embedding_dim,
+                 max_input_length, num_layer, idx_layer, *, num_splits=0, _sized_by_query_heads=False,
+                 rotary_cos_table=None, rotary_sin_table=None, softmax_scale=None, kv_layout="blmhd",
+                 block_table=None, num_heads_kv=None):
+    """One decode step (see include/star_flash_attn.h, sfa_decode).  Returns `o` (same tensor).
+    kv_layout: "blmhd" = the reference's [B, L, M, H, D] caches; "blhmd" = head-major [B, L, H, M, D];
+    "paged" = page pools [num_pages, L, page_size, H, D] addressed through block_table (int32
+    [B, pages_per_seq]); memory_max_len is then the capacity of one sequence.
+    num_heads_kv (grouped queries, an extension): qkv is then [B, num_heads + 2*num_heads_kv, D] (q heads,
+    k heads, v heads), k_bias / v_bias and the caches carry num_heads_kv heads."""
+    lib = _lib.load()
+    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
+                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
+                                      kv_layout, block_table, num_heads_kv)
+    dev = qkv.device
     with torch.cuda.device(dev):
         # the library sizes the split count by the KV heads (one workgroup serves a whole group)
         S = int(num_splits) if num_splits and num_splits > 0 else lib.sfa_decode_auto_splits(B, Hkv, D, M)
@@ -124,32 +162,44 @@ def flash_decode(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_
             S = 0
             ws = torch.empty(lib.sfa_decode_workspace_bytes(B, H, D, M, 0), dtype=torch.uint8, device=dev)
             _lib.check(lib.sfa_decode_reset_status(ctypes.c_void_p(ws.data_ptr()), _stream_ptr(dev)))
-        a = _lib.DecodeArgs()
-        a.qkv = qkv.data_ptr()
-        a.q_bias, a.k_bias, a.v_bias = (b.data_ptr() if b is not None else None for b in biases)
-        a.o = o.data_ptr()
-        a.seq_len = seq_len.data_ptr()
-        a.k_cache_table = k_cache_table.data_ptr()
-        a.v_cache_table = v_cache_table.data_ptr()
-        a.rotary_cos_table = rotary_cos_table.data_ptr() if rotary_cos_table is not None else None
-        a.rotary_sin_table = rotary_sin_table.data_ptr() if rotary_sin_table is not None else None
-        a.batch_size, a.memory_max_len, a.num_heads, a.head_dim = B, M, H, D
-        a.head_dim_inv = float(softmax_scale) if softmax_scale else 1.0 / math.sqrt(D)
-        a.rotary_embedding_dim = int(rotary_embedding_dim)
-        a.max_input_length = int(max_input_length)
         a.stride = (H + 2 * Hkv) * D
-        a.num_heads_kv = Hkv
-        a.num_layer, a.idx_layer = L, int(idx_layer)
         a.num_splits = S
-        a.dtype = _DTYPES[dt]
         a.workspace = ws.data_ptr()
         a.workspace_bytes = ws.numel()
-        a.kv_layout = _lib.KV_LAYOUTS[kv_layout]
-        if kv_layout == "paged":
-            a.page_size, a.num_pages = page_size, num_pages
-            a.block_table = block_table.data_ptr()
-            a.block_table_stride = int(block_table.shape[1])
         _lib.check(lib.sfa_decode(ctypes.byref(a), _stream_ptr(dev)))
+        if _sync_checks:
+            check_decode_status(dev)
+    return o
+
+
+def flash_decode_chunk(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o,
+                       batch_size, memory_max_len, num_heads, head_dim, rotary_embedding_dim,
+                       max_input_length, num_layer, idx_layer, *, num_splits=0,
+                       rotary_cos_table=None, rotary_sin_table=None, softmax_scale=None, kv_layout="blmhd",
+                       block_table=None, num_heads_kv=None):
+    """n new tokens per sequence in one call (include/star_flash_attn.h, sfa_decode_chunk): the same arguments as
+    flash_decode and the result of n successive flash_decode calls.  qkv is [B, n, 3, H, D] (grouped queries:
+    [B, n, H + 2*num_heads_kv, D]), o is [B, n, H, D]; n = qkv.shape[1].  Token t of sequence b is rotated at and
+    appended to position seq_len[b] + t and attends to the cache rows [0, seq_len[b] + t].  seq_len is not
+    incremented.  Ragged prompts: pad to a common n (the rows past a sequence's real length are overwritten by the
+    decode steps that follow, before anything reads them).  Returns `o`."""
+    lib = _lib.load()
+    _require(isinstance(qkv, torch.Tensor) and qkv.dim() in (4, 5),
+             f"qkv must be [B, n, 3, H, D] or [B, n, H + 2*Hkv, D] (got {tuple(getattr(qkv, 'shape', ()))})")
+    n = int(qkv.shape[1])
+    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
+                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
+                                      kv_layout, block_table, num_heads_kv, tokens=n)
+    dev = qkv.device
+    with torch.cuda.device(dev):
+        S = int(num_splits) if num_splits and num_splits > 0 else 0
+        ws = _workspace(dev, lib.sfa_decode_chunk_workspace_bytes(B, H, Hkv, D, M, n, S))
+        a.stride = 0                        # n * (H + 2*Hkv) * D, computed by the library in 64 bit
+        a.num_splits = S
+        a.workspace = ws.data_ptr()
+        a.workspace_bytes = ws.numel()
+        _lib.check(lib.sfa_decode_chunk(ctypes.byref(a), n, 0, _stream_ptr(dev)))
         if _sync_checks:
             check_decode_status(dev)
     return o
