@@ -182,7 +182,7 @@ int sfa_decode(const sfa_decode_args *args, void *stream);
  * between batches (0 => n * qkv_token_stride), qkv_token_stride = elements between tokens (0 => (H + 2*Hkv) *
  * head_dim); args->o is [batch, n, num_heads, head_dim], contiguous.  Every other field of sfa_decode_args keeps its
  * sfa_decode meaning; head_dim 64 or 128 (256 returns SFA_ERR_UNSUPPORTED_HEAD_DIM).  num_tokens = 0 does nothing.
- * Ragged prompts: pad every sequence to a common n.  The rows written past a sequence's real length land at
+ * Ragged prompts: use sfa_decode_varlen (below), or pad every sequence to a common n.  The rows written past a sequence's real length land at
  * positions >= its next seq_len, so the following decode steps overwrite them before anything reads them, and
  * causality keeps the real tokens' outputs independent of the padding.  With a paged cache the table must map the
  * padded rows [pos, pos + n) to valid pages too.
@@ -196,6 +196,40 @@ int sfa_decode(const sfa_decode_args *args, void *stream);
 int    sfa_decode_chunk(const sfa_decode_args *args, int num_tokens, int64_t qkv_token_stride, void *stream);
 size_t sfa_decode_chunk_workspace_bytes(int batch_size, int num_heads, int num_heads_kv, int head_dim,
                                         int memory_max_len, int num_tokens, int num_splits);
+
+/* ---- decode varlen: a ragged, packed batch of new tokens in one call -------------- */
+/*
+ * sfa_decode_chunk with a token count of its own for every sequence: a mix of prompt chunks, speculative verification
+ * and plain decode in one call, with no padding.
+ *   cu_tokens      device int32 [batch_size + 1], cu_tokens[0] = 0, non-decreasing: sequence b owns the packed rows
+ *                  [cu_tokens[b], cu_tokens[b+1]) of qkv and o; n_b is their count.  Read on the device only: the call
+ *                  allocates nothing, never synchronises, and a captured graph may be replayed with other contents.
+ *   total_tokens   host value: the rows of qkv and o, >= cu_tokens[batch_size].  It sizes the grid and the workspace.
+ *   qkv            [total_tokens, 3, num_heads, head_dim] (grouped: [total_tokens, H + 2*Hkv, head_dim]),
+ *                  qkv_token_stride elements between tokens (0 => dense); args->stride must be 0
+ *   o              [total_tokens, num_heads, head_dim], contiguous
+ * Packed row cu_tokens[b] + t, t < n_b, is token t of sfa_decode_chunk at pos = seq_len[b]: rotated at pos + t,
+ * appended to cache row pos + t (every kv_layout), attends to [0, pos + t]; bias, rotary tables, partial rotary,
+ * grouped queries, fp16 / bf16 and head_dim 64 / 128 as there (256 returns SFA_ERR_UNSUPPORTED_HEAD_DIM).  seq_len is
+ * not incremented.  total_tokens = 0 does nothing.
+ * Per sequence:
+ *   n_b == 0       the sequence takes no part: nothing of it is read or written, seq_len[b] is not looked at.
+ *   otherwise      it needs 0 <= pos and pos + n_b <= memory_max_len, and (paged) valid pages for its own rows
+ *                  [pos, pos + n_b) only.  No cache row at or past pos + n_b is written.
+ *   rejected       (pos out of range, or an append page outside the pool): cache untouched, its n_b rows of o NaN,
+ *                  SFA_ERR_SEQ_LEN_RANGE / SFA_ERR_BLOCK_TABLE_RANGE in the sticky status word, as sfa_decode_chunk.
+ *                  A bad page that is only read behaves as in sfa_decode_chunk.
+ *   bad cu_tokens  cu_tokens[b+1] < cu_tokens[b], cu_tokens[b] < 0 or cu_tokens[b+1] > total_tokens: the sequence is
+ *                  skipped with nothing written (o included) and SFA_ERR_SEQ_LEN_RANGE is raised.
+ * Workspace: the status block, the plan (one entry per attention workgroup slot, total_tokens * G / 256 + batch_size
+ * of them), the rotated Q packed over tokens, then (split key range) fp32 partials.  sfa_decode_varlen_workspace_bytes
+ * depends on total_tokens, not on how the tokens are spread over the sequences (num_splits <= 0: the library's choice).
+ * The same workspace (status word) may serve sfa_decode and sfa_decode_chunk calls on the same stream.
+ */
+int    sfa_decode_varlen(const sfa_decode_args *args, const void *cu_tokens, int total_tokens,
+                         int64_t qkv_token_stride, void *stream);
+size_t sfa_decode_varlen_workspace_bytes(int batch_size, int num_heads, int num_heads_kv, int head_dim,
+                                         int memory_max_len, int total_tokens, int num_splits);
 
 /* ---- prefill: O = softmax(mask(Q K^T * scale)) V ------------------------------- */
 /*

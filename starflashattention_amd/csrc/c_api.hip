@@ -109,14 +109,110 @@ static DecodeKernelParams decode_params(const sfa_decode_args *a, int hkv, int p
 // idle, aim for ~256 workgroups, keep every split at least 512 cache rows (8 tiles) of memory_max_len long and at
 // most 32 splits.  The split count is chosen on the host from memory_max_len; the device splits the actual
 // seq_len[b] + n keys, so a split past a sequence's keys only writes an empty partial.
-static int chunk_auto_splits(int B, int Hkv, int rows, int M) {
-    const long long wgs = (long long)B * Hkv * ((rows + 255) / 256);
+static int splits_for_workgroups(long long wgs, int M) {
     long long s = (256 + wgs - 1) / wgs;
     const long long cap = M / 512 > 1 ? M / 512 : 1;
     if (s > cap) s = cap;
     if (s > 32) s = 32;
     if (s < 1) s = 1;
     return (int)s;
+}
+static int chunk_auto_splits(int B, int Hkv, int rows, int M) {
+    return splits_for_workgroups((long long)B * Hkv * ((rows + 255) / 256), M);
+}
+
+// sfa_decode_varlen: the attention grid is bound * Hkv * S workgroups with bound = total_tokens * G / 256 + batch_size plan slots
+// (sfa_host.h); chunk_auto_splits' rule with the workgroup count taken from that bound.
+static int varlen_plan_bound(int B, long long rows) { return (int)(rows / 256 + B); }
+static int varlen_auto_splits(int B, int Hkv, long long rows, int M) {
+    return splits_for_workgroups((long long)varlen_plan_bound(B, rows) * Hkv, M);
+}
+
+// What sfa_decode_chunk and sfa_decode_varlen check alike, before any HIP call, and what they derive on the way.  FN
+// names the entry point in the error text; COUNT is its token count (COUNT_NAME: num_tokens per sequence, or, PACKED,
+// total_tokens over all sequences).
+struct TokenCall {
+    int hkv, group, page_shift;
+    long long tok, stride;      // elements between tokens / batches of qkv
+};
+static int validate_token_call(const char *fn, const sfa_decode_args *a, const char *count_name, int count, bool packed,
+                               int64_t qkv_token_stride, TokenCall *out) {
+    if (!a) return fail(SFA_ERR_NULL_POINTER, "%s: args is NULL", fn);
+    if (!a->qkv || !a->o || !a->seq_len || !a->k_cache_table || !a->v_cache_table)
+        return fail(SFA_ERR_NULL_POINTER, "%s: qkv/o/seq_len/k_cache_table/v_cache_table must be non-NULL", fn);
+    if ((a->rotary_cos_table == nullptr) != (a->rotary_sin_table == nullptr))
+        return fail(SFA_ERR_NULL_POINTER, "%s: give both rotary tables or neither", fn);
+    if (count < 0) return fail(SFA_ERR_BAD_SHAPE, "%s: %s=%d < 0", fn, count_name, count);
+    if (a->batch_size < 0 || a->batch_size > 65535 || a->num_heads <= 0 || a->memory_max_len <= 0 || a->num_layer <= 0)
+        return fail(SFA_ERR_BAD_SHAPE,
+                    "%s: batch_size=%d (<= 65535) num_heads=%d memory_max_len=%d num_layer=%d", fn,
+                    a->batch_size, a->num_heads, a->memory_max_len, a->num_layer);
+    if (a->idx_layer < 0 || a->idx_layer >= a->num_layer)
+        return fail(SFA_ERR_BAD_SHAPE, "%s: idx_layer=%d outside [0, num_layer=%d)", fn, a->idx_layer,
+                    a->num_layer);
+    if (a->head_dim == 256)
+        return fail(SFA_ERR_UNSUPPORTED_HEAD_DIM,
+                    "%s: head_dim 256 is not supported by the chunk path yet (64 or 128; sfa_decode "
+                    "serves 256 one token at a time)", fn);
+    if (a->head_dim != 64 && a->head_dim != 128)
+        return fail(SFA_ERR_UNSUPPORTED_HEAD_DIM, "%s: head_dim %d not in {64, 128}", fn, a->head_dim);
+    if (a->rotary_embedding_dim < 0 || a->rotary_embedding_dim > a->head_dim || (a->rotary_embedding_dim & 1))
+        return fail(SFA_ERR_BAD_SHAPE, "%s: rotary_embedding_dim=%d must be even and in [0, head_dim]", fn,
+                    a->rotary_embedding_dim);
+    if (a->dtype != SFA_DTYPE_FP16 && a->dtype != SFA_DTYPE_BF16)
+        return fail(SFA_ERR_BAD_DTYPE, "%s: dtype %d is not fp16(0)/bf16(1)", fn, a->dtype);
+    const int hkv = a->num_heads_kv > 0 ? a->num_heads_kv : a->num_heads;
+    const int group = hkv > 0 ? a->num_heads / hkv : 0;
+    if (a->num_heads_kv < 0 || group * hkv != a->num_heads ||
+        (group != 1 && group != 2 && group != 4 && group != 8 && group != 16))
+        return fail(SFA_ERR_BAD_SHAPE, "%s: num_heads=%d / num_heads_kv=%d must be 1, 2, 4, 8 or 16", fn,
+                    a->num_heads, a->num_heads_kv);
+    const long long row = (long long)(a->num_heads + 2 * hkv) * a->head_dim;    // packed q,k,v of one token
+    const long long tok = qkv_token_stride > 0 ? qkv_token_stride : row;
+    if (tok < row || (tok % 8) != 0)
+        return fail(SFA_ERR_BAD_SHAPE,
+                    "%s: qkv_token_stride %lld must be >= (H + 2*Hkv)*D and a multiple of 8", fn, tok);
+    if (packed && a->stride != 0)
+        return fail(SFA_ERR_BAD_SHAPE, "%s: args->stride=%d must be 0 (the tokens of all sequences are packed)", fn,
+                    a->stride);
+    const long long stride = a->stride > 0 ? a->stride : (long long)count * tok;
+    if ((count > 0 && stride < (count - 1) * tok + row) || (stride % 8) != 0)
+        return fail(SFA_ERR_BAD_SHAPE,
+                    "%s: qkv stride %lld must be >= (num_tokens-1)*token_stride + (H + 2*Hkv)*D and a "
+                    "multiple of 8", fn, stride);
+    // (packed: the plan kernel sums up to 256 sequences' q-tiles of garbage cu_tokens in an int)
+    if ((long long)count * group > (packed ? INT_MAX / 2 : INT_MAX))
+        return fail(SFA_ERR_BAD_SHAPE, "%s: %s * group = %lld query rows per kv head is too many", fn, count_name,
+                    (long long)count * group);
+    if (a->num_splits > 1024)
+        return fail(SFA_ERR_BAD_SHAPE, "%s: num_splits=%d > 1024", fn, a->num_splits);
+    if (a->kv_layout != SFA_KV_BLMHD && a->kv_layout != SFA_KV_BLHMD && a->kv_layout != SFA_KV_PAGED)
+        return fail(SFA_ERR_BAD_SHAPE,
+                    "%s: kv_layout %d is not SFA_KV_BLMHD(0)/SFA_KV_BLHMD(1)/SFA_KV_PAGED(2)", fn, a->kv_layout);
+    // the attention kernel addresses the 64 rows of a tile with 32-bit lane offsets
+    if (a->kv_layout != SFA_KV_BLHMD && 128ll * hkv * a->head_dim >= (1ll << 31))
+        return fail(SFA_ERR_BAD_SHAPE, "%s: num_heads_kv * head_dim = %lld too large", fn,
+                    (long long)hkv * a->head_dim);
+    int page_shift = 0;
+    if (a->kv_layout == SFA_KV_PAGED) {
+        if (!a->block_table) return fail(SFA_ERR_NULL_POINTER, "%s: kv_layout PAGED needs block_table", fn);
+        if (a->page_size < 16 || (a->page_size & (a->page_size - 1)))
+            return fail(SFA_ERR_BAD_SHAPE, "%s: page_size=%d must be a power of two >= 16", fn, a->page_size);
+        while ((1 << page_shift) < a->page_size) ++page_shift;
+        if (a->num_pages <= 0 || (long long)a->block_table_stride * a->page_size < (long long)a->memory_max_len)
+            return fail(SFA_ERR_BAD_SHAPE,
+                        "%s: num_pages=%d, block_table_stride=%d * page_size=%d must cover memory_max_len=%d", fn,
+                        a->num_pages, a->block_table_stride, a->page_size, a->memory_max_len);
+        if ((uintptr_t)a->block_table & 3)
+            return fail(SFA_ERR_BAD_SHAPE, "%s: block_table must be 4-byte aligned", fn);
+    }
+    const uintptr_t align_or = (uintptr_t)a->qkv | (uintptr_t)a->o | (uintptr_t)a->k_cache_table |
+                               (uintptr_t)a->v_cache_table | (uintptr_t)a->q_bias | (uintptr_t)a->k_bias |
+                               (uintptr_t)a->v_bias;
+    if (align_or & 15) return fail(SFA_ERR_BAD_SHAPE, "%s: tensors must be 16-byte aligned", fn);
+    out->hkv = hkv, out->group = group, out->page_shift = page_shift;
+    out->tok = tok, out->stride = stride;
+    return SFA_OK;
 }
 
 }  // namespace sfa
@@ -318,76 +414,11 @@ size_t sfa_decode_chunk_workspace_bytes(int batch_size, int num_heads, int num_h
 }
 
 int sfa_decode_chunk(const sfa_decode_args *a, int num_tokens, int64_t qkv_token_stride, void *stream) {
-    if (!a) return fail(SFA_ERR_NULL_POINTER, "sfa_decode_chunk: args is NULL");
-    if (!a->qkv || !a->o || !a->seq_len || !a->k_cache_table || !a->v_cache_table)
-        return fail(SFA_ERR_NULL_POINTER, "sfa_decode_chunk: qkv/o/seq_len/k_cache_table/v_cache_table must be non-NULL");
-    if ((a->rotary_cos_table == nullptr) != (a->rotary_sin_table == nullptr))
-        return fail(SFA_ERR_NULL_POINTER, "sfa_decode_chunk: give both rotary tables or neither");
-    if (num_tokens < 0) return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk: num_tokens=%d < 0", num_tokens);
-    if (a->batch_size < 0 || a->batch_size > 65535 || a->num_heads <= 0 || a->memory_max_len <= 0 || a->num_layer <= 0)
-        return fail(SFA_ERR_BAD_SHAPE,
-                    "sfa_decode_chunk: batch_size=%d (<= 65535) num_heads=%d memory_max_len=%d num_layer=%d",
-                    a->batch_size, a->num_heads, a->memory_max_len, a->num_layer);
-    if (a->idx_layer < 0 || a->idx_layer >= a->num_layer)
-        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk: idx_layer=%d outside [0, num_layer=%d)", a->idx_layer,
-                    a->num_layer);
-    if (a->head_dim == 256)
-        return fail(SFA_ERR_UNSUPPORTED_HEAD_DIM,
-                    "sfa_decode_chunk: head_dim 256 is not supported by the chunk path yet (64 or 128; sfa_decode "
-                    "serves 256 one token at a time)");
-    if (a->head_dim != 64 && a->head_dim != 128)
-        return fail(SFA_ERR_UNSUPPORTED_HEAD_DIM, "sfa_decode_chunk: head_dim %d not in {64, 128}", a->head_dim);
-    if (a->rotary_embedding_dim < 0 || a->rotary_embedding_dim > a->head_dim || (a->rotary_embedding_dim & 1))
-        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk: rotary_embedding_dim=%d must be even and in [0, head_dim]",
-                    a->rotary_embedding_dim);
-    if (a->dtype != SFA_DTYPE_FP16 && a->dtype != SFA_DTYPE_BF16)
-        return fail(SFA_ERR_BAD_DTYPE, "sfa_decode_chunk: dtype %d is not fp16(0)/bf16(1)", a->dtype);
-    const int hkv = a->num_heads_kv > 0 ? a->num_heads_kv : a->num_heads;
-    const int group = hkv > 0 ? a->num_heads / hkv : 0;
-    if (a->num_heads_kv < 0 || group * hkv != a->num_heads ||
-        (group != 1 && group != 2 && group != 4 && group != 8 && group != 16))
-        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk: num_heads=%d / num_heads_kv=%d must be 1, 2, 4, 8 or 16",
-                    a->num_heads, a->num_heads_kv);
-    const long long row = (long long)(a->num_heads + 2 * hkv) * a->head_dim;    // packed q,k,v of one token
-    const long long tok = qkv_token_stride > 0 ? qkv_token_stride : row;
-    if (tok < row || (tok % 8) != 0)
-        return fail(SFA_ERR_BAD_SHAPE,
-                    "sfa_decode_chunk: qkv_token_stride %lld must be >= (H + 2*Hkv)*D and a multiple of 8", tok);
-    const long long stride = a->stride > 0 ? a->stride : (long long)num_tokens * tok;
-    if ((num_tokens > 0 && stride < (num_tokens - 1) * tok + row) || (stride % 8) != 0)
-        return fail(SFA_ERR_BAD_SHAPE,
-                    "sfa_decode_chunk: qkv stride %lld must be >= (num_tokens-1)*token_stride + (H + 2*Hkv)*D and a "
-                    "multiple of 8", stride);
-    if ((long long)num_tokens * group > INT_MAX)
-        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk: num_tokens * group = %lld query rows per kv head is too many",
-                    (long long)num_tokens * group);
-    if (a->num_splits > 1024)
-        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk: num_splits=%d > 1024", a->num_splits);
-    if (a->kv_layout != SFA_KV_BLMHD && a->kv_layout != SFA_KV_BLHMD && a->kv_layout != SFA_KV_PAGED)
-        return fail(SFA_ERR_BAD_SHAPE,
-                    "sfa_decode_chunk: kv_layout %d is not SFA_KV_BLMHD(0)/SFA_KV_BLHMD(1)/SFA_KV_PAGED(2)", a->kv_layout);
-    // the attention kernel addresses the 64 rows of a tile with 32-bit lane offsets
-    if (a->kv_layout != SFA_KV_BLHMD && 128ll * hkv * a->head_dim >= (1ll << 31))
-        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk: num_heads_kv * head_dim = %lld too large",
-                    (long long)hkv * a->head_dim);
-    int page_shift = 0;
-    if (a->kv_layout == SFA_KV_PAGED) {
-        if (!a->block_table) return fail(SFA_ERR_NULL_POINTER, "sfa_decode_chunk: kv_layout PAGED needs block_table");
-        if (a->page_size < 16 || (a->page_size & (a->page_size - 1)))
-            return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk: page_size=%d must be a power of two >= 16", a->page_size);
-        while ((1 << page_shift) < a->page_size) ++page_shift;
-        if (a->num_pages <= 0 || (long long)a->block_table_stride * a->page_size < (long long)a->memory_max_len)
-            return fail(SFA_ERR_BAD_SHAPE,
-                        "sfa_decode_chunk: num_pages=%d, block_table_stride=%d * page_size=%d must cover memory_max_len=%d",
-                        a->num_pages, a->block_table_stride, a->page_size, a->memory_max_len);
-        if ((uintptr_t)a->block_table & 3)
-            return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk: block_table must be 4-byte aligned");
-    }
-    const uintptr_t align_or = (uintptr_t)a->qkv | (uintptr_t)a->o | (uintptr_t)a->k_cache_table |
-                               (uintptr_t)a->v_cache_table | (uintptr_t)a->q_bias | (uintptr_t)a->k_bias |
-                               (uintptr_t)a->v_bias;
-    if (align_or & 15) return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk: tensors must be 16-byte aligned");
+    TokenCall tc;
+    if (const int rc = validate_token_call("sfa_decode_chunk", a, "num_tokens", num_tokens, false, qkv_token_stride, &tc))
+        return rc;
     if (a->batch_size == 0 || num_tokens == 0) return SFA_OK;
+    const int hkv = tc.hkv, group = tc.group;
 
     const int rows = num_tokens * group;
     const int S = a->num_splits > 0 ? a->num_splits : chunk_auto_splits(a->batch_size, hkv, rows, a->memory_max_len);
@@ -402,18 +433,81 @@ int sfa_decode_chunk(const sfa_decode_args *a, int num_tokens, int64_t qkv_token
 
     ChunkKernelParams p;
     memset(&p, 0, sizeof(p));
-    p.d = decode_params(a, hkv, page_shift, S, stride);
+    p.d = decode_params(a, hkv, tc.page_shift, S, tc.stride);
     char *ws = (char *)a->workspace;
     const size_t bhr = (size_t)a->batch_size * hkv * rows;
     const size_t q_bytes = align_up(bhr * a->head_dim * sizeof(uint16_t), 256);
     p.q_rot = (uint16_t *)(ws + kStatusBytes);
     p.d.part_o = (float *)(ws + kStatusBytes + q_bytes);
     p.d.part_ml = (float2 *)(ws + kStatusBytes + q_bytes + align_up(bhr * S * a->head_dim * sizeof(float), 256));
-    p.tok_stride = tok;
+    p.tok_stride = tc.tok;
     p.n = num_tokens;
     p.G = group;
     p.R = rows;
     return launch_decode_chunk(p, a->dtype, a->head_dim, (hipStream_t)stream);
+}
+
+size_t sfa_decode_varlen_workspace_bytes(int batch_size, int num_heads, int num_heads_kv, int head_dim,
+                                         int memory_max_len, int total_tokens, int num_splits) {
+    if (batch_size <= 0 || num_heads <= 0 || head_dim <= 0 || total_tokens <= 0) return kStatusBytes;
+    const int hkv = num_heads_kv > 0 ? num_heads_kv : num_heads;
+    const long long rows = (long long)total_tokens * (num_heads / hkv);     // packed query rows per kv head
+    const int S = num_splits > 0 ? num_splits : varlen_auto_splits(batch_size, hkv, rows, memory_max_len);
+    const size_t hr = (size_t)hkv * rows;
+    size_t bytes = kStatusBytes + align_up((size_t)varlen_plan_bound(batch_size, rows) * sizeof(int2), 256);    // plan
+    bytes += align_up(hr * head_dim * sizeof(uint16_t), 256);               // rotated Q
+    if (S > 1) {
+        bytes += align_up(hr * S * head_dim * sizeof(float), 256);
+        bytes += align_up(hr * S * sizeof(float2), 256);
+    }
+    return bytes;
+}
+
+int sfa_decode_varlen(const sfa_decode_args *a, const void *cu_tokens, int total_tokens, int64_t qkv_token_stride,
+                      void *stream) {
+    TokenCall tc;
+    if (a && !cu_tokens) return fail(SFA_ERR_NULL_POINTER, "sfa_decode_varlen: cu_tokens is NULL");
+    if (const int rc = validate_token_call("sfa_decode_varlen", a, "total_tokens", total_tokens, true, qkv_token_stride,
+                                           &tc))
+        return rc;
+    if ((uintptr_t)cu_tokens & 3) return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_varlen: cu_tokens must be 4-byte aligned");
+    const long long rows = (long long)total_tokens * tc.group;
+    if (a->batch_size == 0 || total_tokens == 0) return SFA_OK;
+
+    const int hkv = tc.hkv;
+    const int S = a->num_splits > 0 ? a->num_splits : varlen_auto_splits(a->batch_size, hkv, rows, a->memory_max_len);
+    // the attention kernel's 1-D grid: one workgroup per (plan slot, kv head, split)
+    if ((long long)varlen_plan_bound(a->batch_size, rows) * hkv * S > INT_MAX)
+        return fail(SFA_ERR_BAD_SHAPE,
+                    "sfa_decode_varlen: total_tokens=%d, batch_size=%d, num_heads_kv=%d and num_splits=%d need more than "
+                    "2^31 - 1 attention workgroups", total_tokens, a->batch_size, hkv, S);
+    const size_t need = sfa_decode_varlen_workspace_bytes(a->batch_size, a->num_heads, hkv, a->head_dim,
+                                                          a->memory_max_len, total_tokens, S);
+    if (!a->workspace) return fail(SFA_ERR_NULL_POINTER, "sfa_decode_varlen: workspace is NULL (need %zu bytes)", need);
+    if (a->workspace_bytes < need)
+        return fail(SFA_ERR_WORKSPACE_TOO_SMALL, "sfa_decode_varlen: workspace has %zu bytes, need %zu",
+                    a->workspace_bytes, need);
+    if ((uintptr_t)a->workspace & 255)
+        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_varlen: workspace must be 256-byte aligned");
+
+    VarlenKernelParams p;
+    memset(&p, 0, sizeof(p));
+    p.c.d = decode_params(a, hkv, tc.page_shift, S, 0);
+    p.c.tok_stride = tc.tok;
+    p.c.G = tc.group;
+    p.cu_tokens = (const int32_t *)cu_tokens;
+    p.rows = rows;
+    p.total = total_tokens;
+    p.bound = varlen_plan_bound(a->batch_size, rows);
+    char *ws = (char *)a->workspace + kStatusBytes;     // the layout of sfa_host.h
+    const size_t hr = (size_t)hkv * rows;
+    p.plan = (int2 *)ws;
+    ws += align_up((size_t)p.bound * sizeof(int2), 256);
+    p.c.q_rot = (uint16_t *)ws;
+    ws += align_up(hr * a->head_dim * sizeof(uint16_t), 256);
+    p.c.d.part_o = (float *)ws;
+    p.c.d.part_ml = (float2 *)(ws + align_up(hr * S * a->head_dim * sizeof(float), 256));
+    return launch_decode_varlen(p, a->dtype, a->head_dim, (hipStream_t)stream);
 }
 
 int sfa_prefill_fwd(const sfa_prefill_args *a, void *stream) {

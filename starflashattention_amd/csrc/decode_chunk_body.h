@@ -1,0 +1,435 @@
+// The three kernels of the multi-token decode step, shared by sfa_decode_chunk (decode_chunk_kernel.hip: the same n
+// for every sequence) and sfa_decode_varlen (decode_varlen_kernel.hip: a ragged, packed batch).  What differs between
+// the two -- how many tokens a sequence has, where its packed rows of qkv / o / the rotated Q / the partials are, and
+// which (sequence, q-tile) a workgroup serves -- sits behind one policy, GEO:
+//
+//   using Params                       the kernel argument; chunk(gp) is its ChunkKernelParams
+//   prologue(gp, b, t, n) -> bool      the (sequence, token) of this prologue workgroup and the sequence's token count;
+//                                      false: the packed row belongs to no sequence, touch nothing
+//   qkv_off(gp, b, t)                  element offset of token t of sequence b in qkv
+//   attn(gp, b, qt, hs, n, R) -> bool  the (sequence, q-tile) and hs = kv head * S + split of this attention workgroup;
+//                                      false: an empty plan slot
+//   q_row(gp, b, hk, r)                row of the rotated Q that holds query row r = t*G + g of (b, hk)
+//   part_row(gp, b, hk, split, r)      the same for the fp32 partials [.., S, ..]
+//   o_tok(gp, b, t)                    row of o ([rows, H, D]) of token t of sequence b
+//   combine(gp, row, ...) -> bool      the partial group / row / o token / head a combine thread merges
+//
+// With the uniform policy every one of these is the expression the chunk kernels used to spell out, and the kernels
+// compile to the code they compiled to before the split (DESIGN.md lists the resource usage of both).
+#pragma once
+#include "decode_chunk_common.h"
+#include "prefill_core.h"
+
+namespace sfa {
+namespace chunk {
+
+using namespace prefill;
+using decode::pack8;
+using decode::unpack8;
+
+constexpr uint16_t nan_bits(int dtype_id) { return dtype_id == 0 ? 0x7e00 : 0x7fc0; }
+
+template <class GEO, class Tr, int D, bool PAGED>
+__global__ void __launch_bounds__(256)
+chunk_prologue_kernel(const typename GEO::Params gp) {
+    const ChunkKernelParams &cp = GEO::chunk(gp);
+    const DecodeKernelParams &p = cp.d;
+    constexpr int LPR = D / 8;                  // lanes (16 B each) per head row
+    int t, b, n;
+    if (!GEO::prologue(gp, b, t, n)) return;
+    const int pos = p.seq_len[b];
+    const int reject = chunk::reject_code<PAGED>(p, n, b, pos);
+    if (reject) {
+        if (t == 0 && threadIdx.x == 0) atomicOr(p.status, reject);
+        return;
+    }
+    const int row = pos + t;                    // cache row and RoPE position of token t
+    const int Hq = p.H, Hkv = p.Hkv, G = cp.G;
+    const long long src = GEO::qkv_off(gp, b, t);
+    long long kv_off = chunk::head_base<D, PAGED>(p, b, 0);
+    if (PAGED) {
+        const int pg = p.block_table[(long long)b * p.table_stride + (row >> p.page_shift)];   // checked above
+        kv_off += pg * p.page_stride + (long long)(row & ((1 << p.page_shift) - 1)) * p.kv_row_stride;
+    } else {
+        kv_off += (long long)row * p.kv_row_stride;
+    }
+    // cos / sin of this token's pairs, once per workgroup (not once per head: the trig dominated the prologue)
+    __shared__ float cs[D / 2], sn[D / 2];
+    for (int j = threadIdx.x; j < (p.rot_dim >> 1); j += blockDim.x) chunk::rope_cs<Tr>(j, row, p, cs[j], sn[j]);
+    __syncthreads();
+    const int items = (Hq + 2 * Hkv) * LPR;
+    for (int i = threadIdx.x; i < items; i += blockDim.x) {
+        const int hd = i / LPR, sub = i % LPR;
+        const uint4 raw = *reinterpret_cast<const uint4 *>(p.qkv + src + (long long)hd * D + sub * 8);
+        if (hd < Hq + Hkv) {                    // q head or k head: bias, RoPE, round
+            const bool isq = hd < Hq;
+            const int h = isq ? hd : hd - Hq;
+            float x[8];
+            unpack8<Tr>(raw, x);
+            const uint16_t *bias = isq ? p.q_bias : p.k_bias;
+            if (bias) chunk::add_bias8<Tr>(x, bias + (long long)h * D + sub * 8);
+            chunk::rope8(x, sub, p.rot_dim, cs, sn);
+            const uint4 pk = pack8<Tr>(x);
+            if (isq) {
+                const long long r = (long long)t * G + h % G;
+                *reinterpret_cast<uint4 *>(cp.q_rot + GEO::q_row(gp, b, h / G, r) * D + sub * 8) = pk;
+            } else {
+                *reinterpret_cast<uint4 *>(p.k_cache + kv_off + (long long)h * p.kv_head_stride + sub * 8) = pk;
+            }
+        } else {                                // v head: bias only
+            const int h = hd - Hq - Hkv;
+            uint4 pk = raw;
+            if (p.v_bias) {
+                float x[8];
+                unpack8<Tr>(raw, x);
+                chunk::add_bias8<Tr>(x, p.v_bias + (long long)h * D + sub * 8);
+                pk = pack8<Tr>(x);
+            }
+            *reinterpret_cast<uint4 *>(p.v_cache + kv_off + (long long)h * p.kv_head_stride + sub * 8) = pk;
+        }
+    }
+}
+
+// Which (sequence, q-tile, kv head * S + split) a workgroup serves is GEO::attn's business (uniform: blockIdx x = q-tile,
+// heaviest first, y = kv head * S + split, z = batch).
+template <class GEO, class Tr, int D, bool PAGED>
+__global__ void __launch_bounds__(kThreads, 2)
+chunk_attn_kernel(const typename GEO::Params gp) {
+    using Vec = typename Tr::mfma_vec;
+    constexpr int NQB = 1, PF = 2, ORD = 2;     // one 32-row query block per wave, exact scale, staged softmax
+    constexpr int NKS = D / 16;                 // k-steps of Q.K^T
+    constexpr int NDB = D / 32;                 // 32-wide d blocks of O^T
+    constexpr int NPV_ = 2 * NDB;
+    constexpr int CPR = D / 8;                  // 16-B chunks per row
+    constexpr int NLD = kBN * CPR / kThreads;   // chunks staged per thread per tile (2 or 1)
+    constexpr int ROWSTEP = kThreads / CPR;     // row distance between a thread's chunks
+    constexpr int NPS = PAGED ? 4 : 1;          // page slots of a 64-row tile (page_size >= 16)
+    using L = Lds<D>;
+    static_assert(NLD >= 1 && NLD <= 2, "staging registers are named kr0, kr1");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const ChunkKernelParams &cp = GEO::chunk(gp);
+    const DecodeKernelParams &p = cp.d;
+
+    const int S = p.num_splits;
+    int b, qt, hs, ntok, R;                     // ntok new tokens, R = ntok * G query rows per kv head
+    if (!GEO::attn(gp, b, qt, hs, ntok, R)) return;
+    const int hk = hs / S, split = hs % S;
+    const int G = cp.G;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l31 = lane & 31, h2 = lane >> 5;
+    const int q0 = qt * kBM, wq0 = q0 + 32 * wave, qrow = wq0 + l31;
+    const long long prow = GEO::part_row(gp, b, hk, split, 0);     // partial row 0 of (b, hk, split)
+    auto out_row = [&](int r) -> uint16_t * {  // o[b, t, h, :] of query row r = t*G + g
+        return p.o + (GEO::o_tok(gp, b, r / G) * p.H + (long long)hk * G + r % G) * D;
+    };
+
+    const int pos = p.seq_len[b];
+    if (const int reject = chunk::reject_code<PAGED>(p, ntok, b, pos)) {
+        (void)reject;                           // the prologue raised the flag
+        if (qrow < R && h2 == 0) {
+            if (S == 1) {
+                const uint32_t w = nan_bits(Tr::id) * 0x10001u;
+                uint16_t *orow = out_row(qrow);
+#pragma unroll
+                for (int c = 0; c < D / 8; ++c) *reinterpret_cast<uint4 *>(orow + 8 * c) = make_uint4(w, w, w, w);
+            } else {
+                p.part_ml[prow + qrow] = make_float2(0.f, __builtin_nanf(""));
+            }
+        }
+        return;
+    }
+
+    // ---- the key range of this workgroup: tiles [ts0, wg_end) of the Kb = pos + n keys ----
+    const int Kb = pos + ntok;
+    const int ntot = (Kb + kBN - 1) / kBN;
+    const int per = (ntot + S - 1) / S;         // tiles per split
+    const int ts0 = split * per;
+    const int rlast = min(q0 + kBM, R) - 1;     // last query row of the q-tile
+    const int wg_end = min(min(ntot, ts0 + per), (pos + rlast / G) / kBN + 1);
+    const int nt = max(0, wg_end - ts0);        // tiles the workgroup stages (workgroup-uniform)
+    int ntw = 0;                                // tiles this wave computes on (wave-uniform)
+    if (wq0 < R) ntw = max(0, min(wg_end, (pos + min(wq0 + 31, R - 1) / G) / kBN + 1) - ts0);
+    int lim[NQB];                               // last visible key of this lane's row
+    lim[0] = pos + min(qrow, R - 1) / G;
+    const int wlim = pos + min(wq0, R - 1) / G; // the smallest limit of the wave's rows
+    // bit 0 set: the 32 keys starting at KBASE need masking for this wave's rows (lim <= Kb - 1 always)
+    auto mask_bits = [&](int kbase) -> int { return kbase + 31 > wlim ? 1 : 0; };
+
+    // ---- staging: thread owns chunks (row st_row + i*ROWSTEP, chunk st_ch), i < NLD, of every tile ----
+    const int st_row = tid / CPR, st_ch = tid % CPR;
+    const long long rsb = 2 * p.kv_row_stride;  // bytes between cache rows (of one page)
+    const long long hb = chunk::head_base<D, PAGED>(p, b, hk);
+    const char *const kg = reinterpret_cast<const char *>(p.k_cache + hb);
+    const char *const vg = reinterpret_cast<const char *>(p.v_cache + hb);
+    char *const k_w = smem + L::KS * st_row + 16 * st_ch;
+    char *const v_w = smem + L::V_BASE + L::VS * st_row + 16 * st_ch;
+    uint4 kr0, kr1, vr0, vr1;       // plain scalars: arrays of these ended up in scratch (prefill_kernel.hip)
+    kr0 = kr1 = vr0 = vr1 = make_uint4(0, 0, 0, 0);
+    // Rows of a tile: contiguous layouts and pages >= 64 rows hold the whole tile at one base; pages of 16 / 32 rows
+    // split it into 4 / 2 page slots of 1 << psh rows.  Row r of the tile is at slot base (r >> psh) plus the
+    // lane offset (r & (2^psh - 1)) * rsb.  The ragged last tile (Kb % 64 != 0) swaps in row-clamped offsets.
+    const int psh = PAGED ? min(p.page_shift, 6) : 6;
+    const int rmask = (1 << psh) - 1;
+    const int ragged_tile = (Kb % kBN) ? ntot - 1 : -1;
+    const int last0 = Kb - 1 - (ntot - 1) * kBN;            // last valid row of the last tile
+    const int row0_ = st_row, row1_ = st_row + ROWSTEP;
+    const int rr0_ = min(row0_, last0), rr1_ = min(row1_, last0);
+    // (32 bit: 64 rows * rsb < 2^31, checked by sfa_decode_chunk)
+    auto lane_off = [&](int r) -> unsigned { return (unsigned)(r & rmask) * (unsigned)rsb + 16u * st_ch; };
+    const unsigned ow0 = lane_off(row0_), ow1 = lane_off(row1_), or0 = lane_off(rr0_), or1 = lane_off(rr1_);
+    const int sw0 = row0_ >> psh, sw1 = row1_ >> psh, sr0 = rr0_ >> psh, sr1 = rr1_ >> psh;
+    const int32_t *tbl = PAGED ? p.block_table + (long long)b * p.table_stride : nullptr;
+    const int pmask = PAGED ? (1 << p.page_shift) - 1 : 0;
+    int bad_page = 0;
+    // byte offsets (from kg / vg) of the page slots of tile `tile` -- scalar: table entries by s_load
+    auto tile_base = [&](int tile, long long (&o)[NPS]) {
+        const int r0 = tile * kBN;
+        if (!PAGED) {
+            o[0] = (long long)r0 * rsb;
+            return;
+        }
+#pragma unroll
+        for (int j = 0; j < NPS; ++j) {
+            o[j] = 0;
+            if ((j << psh) < kBN) {
+                const int r = min(r0 + (j << psh), Kb - 1);
+                int pg = tbl[r >> p.page_shift];
+                if ((unsigned)pg >= (unsigned)p.num_pages) {    // a READ page outside the pool: not dereferenced
+                    bad_page = 1;
+                    pg = 0;
+                }
+                o[j] = pg * p.page_stride * 2 + (long long)(r0 & pmask) * rsb;
+            }
+        }
+    };
+    auto sel = [&](const long long (&o)[NPS], int s) -> long long {
+        if (NPS == 1) return o[0];
+        return s == 0 ? o[0] : s == 1 ? o[1] : s == 2 ? o[2] : o[3];
+    };
+    constexpr int NOPS = 2 * NLD;   // op n: even = K chunk n/2, odd = V chunk n/2
+    struct TileSrc { long long k[NPS], v[NPS]; bool rk, rv; };
+    auto tile_of = [&](int t) -> int { return min(ts0 + t, wg_end - 1); };  // past the end: re-read the last tile
+    auto tile_src = [&](int pos_k, int pos_v) -> TileSrc {
+        const int tk = tile_of(pos_k), tv = tile_of(pos_v);
+        TileSrc ts;
+        tile_base(tk, ts.k);
+        tile_base(tv, ts.v);
+        ts.rk = tk == ragged_tile;
+        ts.rv = tv == ragged_tile;
+        return ts;
+    };
+    auto ld_k = [&](const TileSrc &ts, int i) -> uint4 {
+        const long long off = i == 0 ? (ts.rk ? sel(ts.k, sr0) + or0 : sel(ts.k, sw0) + ow0)
+                                     : (ts.rk ? sel(ts.k, sr1) + or1 : sel(ts.k, sw1) + ow1);
+        return *reinterpret_cast<const uint4 *>(kg + off);
+    };
+    auto ld_v = [&](const TileSrc &ts, int i) -> uint4 {
+        const long long off = i == 0 ? (ts.rv ? sel(ts.v, sr0) + or0 : sel(ts.v, sw0) + ow0)
+                                     : (ts.rv ? sel(ts.v, sr1) + or1 : sel(ts.v, sw1) + ow1);
+        return *reinterpret_cast<const uint4 *>(vg + off);
+    };
+    auto load_op = [&](int n, const TileSrc &ts) {
+        if (n == 0) kr0 = ld_k(ts, 0);
+        if (n == 1) vr0 = ld_v(ts, 0);
+        if (NLD > 1 && n == 2) kr1 = ld_k(ts, 1);
+        if (NLD > 1 && n == 3) vr1 = ld_v(ts, 1);
+    };
+    auto store_op = [&](int n, int kbuf, int vbuf) {
+        if (n == 0) *reinterpret_cast<uint4 *>(k_w + kbuf) = kr0;
+        if (n == 1) *reinterpret_cast<uint4 *>(v_w + vbuf) = vr0;
+        if (NLD > 1 && n == 2) *reinterpret_cast<uint4 *>(k_w + kbuf + ROWSTEP * L::KS) = kr1;
+        if (NLD > 1 && n == 3) *reinterpret_cast<uint4 *>(v_w + vbuf + ROWSTEP * L::VS) = vr1;
+    };
+
+    const float c2 = p.scale_log2;
+    const char *const k_rd = smem + L::KS * l31 + 16 * h2;                 // K row l31, chunk h2
+    const char *const v_rd = smem + L::V_BASE + L::VS * (4 * h2 + ((lane & 15) >> 2)) +
+                             32 * ((lane >> 4) & 1) + 16 * ((lane & 3) >> 1) + 8 * (lane & 1);
+
+    // ---- Q^T fragments (B operand) from the workspace: lane holds Q[row][16ks + 8*h2 .. +8] ----
+    Vec qf[NQB][NKS];
+    {
+        const uint16_t *qp = cp.q_rot + GEO::q_row(gp, b, hk, min(qrow, R - 1)) * D + 8 * h2;
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) qf[0][ks] = bitcast<Vec>(*reinterpret_cast<const uint4 *>(qp + 16 * ks));
+    }
+
+    Acc<D, NQB> acc;
+#pragma unroll
+    for (int d = 0; d < NDB; ++d)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc.o[0][d][r] = 0.f;
+    acc.msc[0] = ninf();
+    acc.lsum[0] = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc.cinit[0][r] = 0.f;
+
+    if (nt > 0) {
+        // ---- staging prologue (prefill_kernel.hip): stream positions 0 and 1 into LDS, 2 (K) and 1 (V) in flight ----
+        uint4 kx0, kx1;                         // K(1), prologue only
+        {
+            const TileSrc ts0_ = tile_src(0, 0);
+#pragma unroll
+            for (int n = 0; n < NOPS; ++n) load_op(n, ts0_);
+            const TileSrc ts1_ = tile_src(1, 1);
+            kx0 = ld_k(ts1_, 0);
+            kx1 = NLD > 1 ? ld_k(ts1_, 1) : make_uint4(0, 0, 0, 0);
+        }
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) asm volatile("" : "+v"(qf[0][ks]));   // launder: prefill_kernel.hip
+#pragma unroll
+        for (int n = 0; n < NOPS; ++n) store_op(n, 0, 0);
+        *reinterpret_cast<uint4 *>(k_w + L::KTILE) = kx0;
+        if (NLD > 1) *reinterpret_cast<uint4 *>(k_w + L::KTILE + ROWSTEP * L::KS) = kx1;
+        __syncthreads();
+        {
+            const TileSrc ts1 = tile_src(2, 1);
+#pragma unroll
+            for (int n = 0; n < NOPS; ++n) load_op(n, ts1);
+        }
+
+        int kcur = 0, vcur = 0;     // byte offsets of the K and V buffers of stream position t
+        int t = 0;                  // stream position (tile ts0 + t)
+#define SFA_NEXT3(X, TILE) (((X) == 2 * (TILE)) ? 0 : (X) + (TILE))
+#define SFA_ADVANCE()                                                                               \
+    do {                                                                                            \
+        kcur = SFA_NEXT3(kcur, L::KTILE);                                                           \
+        vcur = SFA_NEXT3(vcur, L::VTILE);                                                           \
+    } while (0)
+#define SFA_STAGE_AND_SYNC(T)                                                                       \
+    do {                                                                                            \
+        const int k1_ = SFA_NEXT3(kcur, L::KTILE);                                                  \
+        _Pragma("unroll") for (int n_ = 0; n_ < NOPS; ++n_)                                         \
+            store_op(n_, SFA_NEXT3(k1_, L::KTILE), SFA_NEXT3(vcur, L::VTILE));                      \
+        __syncthreads();                                                                            \
+        const TileSrc ts_ = tile_src((T) + 3, (T) + 2);                                             \
+        _Pragma("unroll") for (int n_ = 0; n_ < NOPS; ++n_) load_op(n_, ts_);                       \
+        SFA_FENCE();                                                                                \
+    } while (0)
+
+        // ---- scores of the first half-tile, first fragments of the second ----
+        f32x16 sA[NQB], sB[NQB];
+        float mxA[NQB] = {ninf()}, mxB[NQB] = {ninf()};
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { sA[0][r] = 0.f; sB[0][r] = 0.f; }
+        Vec kpre[PF];
+#pragma unroll
+        for (int i = 0; i < PF; ++i) kpre[i] = bitcast<Vec>(make_uint4(0, 0, 0, 0));
+        if (ntw > 0) {
+#pragma unroll
+            for (int ks = 0; ks < NKS; ++ks) {
+                const Vec a = bitcast<Vec>(*reinterpret_cast<const uint4 *>(k_rd + kcur + 32 * ks));
+                sA[0] = Tr::mfma32(a, qf[0][ks], sA[0]);
+            }
+#pragma unroll
+            for (int i = 0; i < PF; ++i)
+                kpre[i] = bitcast<Vec>(*reinterpret_cast<const uint4 *>(k_rd + kcur + L::KS * 32 + 32 * i));
+            mxA[0] = lane_rowmax(sA[0]);
+        }
+
+        // ---- FULL steps: this wave needs the next tile as well (prefill_kernel.hip) ----
+        for (; t + 1 < ntw; ++t) {
+            const int k1 = SFA_NEXT3(kcur, L::KTILE), k2 = SFA_NEXT3(k1, L::KTILE);
+            const int v1 = SFA_NEXT3(vcur, L::VTILE);
+            const char *kb = k_rd + kcur, *vb = v_rd + vcur, *kb1 = k_rd + k1;
+            const int kbase = (ts0 + t) * kBN;
+            auto st_hook = [&](int j) {
+#pragma unroll
+                for (int n = j * NOPS / NPV_; n < (j + 1) * NOPS / NPV_; ++n) store_op(n, k2, v1);
+            };
+            h_block<Tr, D, NQB, PF, ORD, 1, 0, true, true>(kb, vb, kb1, qf, sB, sA, acc, c2, mxA, mxB,
+                                                           mask_bits(kbase), kbase, h2, lim, kpre, NoHook(), st_hook);
+            __syncthreads();
+            const TileSrc ts = tile_src(t + 3, t + 2);
+            auto ld_hook = [&](int i) {
+#pragma unroll
+                for (int n = (i - 1) * NOPS / (NKS - 1); n < i * NOPS / (NKS - 1); ++n) load_op(n, ts);
+            };
+            h_block<Tr, D, NQB, PF, ORD, 0, 1, true, true>(kb1, vb, kb1, qf, sA, sB, acc, c2, mxB, mxA,
+                                                           mask_bits(kbase + 32), kbase + 32, h2, lim, kpre, ld_hook);
+            SFA_ADVANCE();
+        }
+        // ---- TAIL step: this wave's last tile ----
+        if (t < ntw) {
+            const char *kb = k_rd + kcur, *vb = v_rd + vcur;
+            const int kbase = (ts0 + t) * kBN;
+            h_block<Tr, D, NQB, PF, ORD, 1, 0, true, false>(kb, vb, kb, qf, sB, sA, acc, c2, mxA, mxB,
+                                                            mask_bits(kbase), kbase, h2, lim, kpre);
+            SFA_STAGE_AND_SYNC(t);
+            h_block<Tr, D, NQB, PF, ORD, 0, 1, false, false>(kb, vb, kb, qf, sA, sB, acc, c2, mxB, mxA,
+                                                             mask_bits(kbase + 32), kbase + 32, h2, lim, kpre);
+            SFA_ADVANCE();
+            ++t;
+        }
+        // ---- idle steps (tiles beyond this wave's causal limit): keep staging for the others ----
+        for (; t < nt; ++t) {
+            SFA_STAGE_AND_SYNC(t);
+            SFA_ADVANCE();
+        }
+#undef SFA_NEXT3
+#undef SFA_ADVANCE
+#undef SFA_STAGE_AND_SYNC
+    }
+
+    // ---- epilogue ----
+    float ltot = half_sum(acc.lsum[0]);
+    if (PAGED && bad_page) {
+        ltot = __builtin_nanf("");
+        if (tid == 0) atomicOr(p.status, 2);
+    }
+    if (qrow < R) {
+        if (S == 1) {
+            // every row sees key 0 (pos >= 0), so ltot > 0 -- or NaN after a bad page
+            store_o_row<Tr, D>(out_row(qrow), acc.o[0], 1.0f / ltot, h2);
+        } else {
+            // un-normalised O^T: lane (l31, h2) holds columns 32d + 8g + 4*h2 + {0..3} in registers 4g..4g+3
+            float *po = p.part_o + (prow + qrow) * D;
+#pragma unroll
+            for (int d = 0; d < NDB; ++d)
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+                    *reinterpret_cast<float4 *>(po + 32 * d + 8 * g + 4 * h2) =
+                        make_float4(acc.o[0][d][4 * g], acc.o[0][d][4 * g + 1], acc.o[0][d][4 * g + 2],
+                                    acc.o[0][d][4 * g + 3]);
+            if (h2 == 0) p.part_ml[prow + qrow] = make_float2(acc.msc[0], ltot);
+        }
+    }
+}
+
+// o[b, t, h, :] = sum_s 2^(m_s - M) o_s / sum_s 2^(m_s - M) l_s    (fp32; an empty split has m = -inf, l = 0)
+template <class GEO, class Tr, int D>
+__global__ void __launch_bounds__(256)
+chunk_combine_kernel(const typename GEO::Params gp) {
+    const ChunkKernelParams &cp = GEO::chunk(gp);
+    const DecodeKernelParams &p = cp.d;
+    constexpr int LPR = D / 8;
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long row = gid / LPR;            // over the rows of the rotated Q
+    const int sub = (int)(gid % LPR);
+    // partials of the row: [grp, S, rows, D] at (grp, s, r); its output: o[tok, head, :]
+    long long grp, rows, r, tok;
+    int head;
+    if (!GEO::combine(gp, row, grp, rows, r, tok, head)) return;
+    const int S = p.num_splits;
+    decode::Stream tot;
+    tot.init();
+    for (int s = 0; s < S; ++s) {
+        const long long idx = (grp * S + s) * rows + r;
+        const float2 ml = p.part_ml[idx];
+        const float *po = p.part_o + idx * D + sub * 8;
+        const float4 a = *reinterpret_cast<const float4 *>(po);
+        const float4 c = *reinterpret_cast<const float4 *>(po + 4);
+        const float a2[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
+        tot.merge(ml.x, ml.y, a2);
+    }
+    const float inv = 1.0f / tot.l;
+    float y[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) y[j] = tot.acc[j] * inv;
+    uint16_t *orow = p.o + (tok * p.H + head) * D;
+    *reinterpret_cast<uint4 *>(orow + sub * 8) = pack8<Tr>(y);
+}
+
+}  // namespace chunk
+}  // namespace sfa

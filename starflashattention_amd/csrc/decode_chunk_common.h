@@ -1,4 +1,4 @@
-// Device helpers of the multi-token decode step (decode_chunk_kernel.hip): the per-element bias / RoPE
+// Device helpers of the multi-token decode step (decode_chunk_body.h): the per-element bias / RoPE
 // arithmetic of the single-token decode kernels, restated once so that a chunk of n tokens writes the cache
 // bytes n successive sfa_decode calls would, and the chunk's rejection rule.
 #pragma once
@@ -46,16 +46,15 @@ __device__ __forceinline__ void rope8(float (&x)[8], int sub, int rot, const flo
     }
 }
 
-// Which sticky status bit sequence b raises before anything is touched (every kernel of the chunk computes the
-// same value): 1 = pos < 0 or pos + n > memory_max_len; 2 = (paged) a block_table entry of a page covering the new
+// Which sticky status bit sequence b, with n >= 1 new tokens, raises before anything is touched (every kernel of the
+// chunk computes the same value): 1 = pos < 0 or pos + n > memory_max_len; 2 = (paged) a block_table entry of a page covering the new
 // rows [pos, pos+n) lies outside the pool.  0 = fine.  Workgroup-collective (all threads must call it).
 template <bool PAGED>
-__device__ __forceinline__ int reject_code(const ChunkKernelParams &cp, int b, int pos) {
-    const DecodeKernelParams &p = cp.d;
-    if (pos < 0 || pos > p.M - cp.n) return 1;
+__device__ __forceinline__ int reject_code(const DecodeKernelParams &p, int n, int b, int pos) {
+    if (pos < 0 || pos > p.M - n) return 1;
     if (PAGED) {
         const int32_t *tbl = p.block_table + (long long)b * p.table_stride;
-        const int first = pos >> p.page_shift, last = (pos + cp.n - 1) >> p.page_shift;
+        const int first = pos >> p.page_shift, last = (pos + n - 1) >> p.page_shift;
         int bad = 0;
         for (int i = first + (int)threadIdx.x; i <= last; i += (int)blockDim.x)
             bad |= (unsigned)tbl[i] >= (unsigned)p.num_pages;

@@ -1,0 +1,174 @@
+// Ragged multi-token decode step (sfa_decode_varlen) for gfx950 (MI355X): sequence b brings n_b = cu_tokens[b+1] -
+// cu_tokens[b] new tokens, packed one after another in qkv / o ([total_tokens, ...]); n_b = 0 takes no part.  One call
+// serves a mix of prompt chunks, speculative verification and plain decode.  Each token gets exactly what
+// sfa_decode_chunk gives it at pos = seq_len[b]; the kernels are the chunk's (decode_chunk_body.h) under the ragged
+// geometry RaggedGeo.
+//
+// Four launches, ordered by the stream alone:
+//   0. varlen_plan_kernel (one workgroup): from cu_tokens, the compact list of (sequence, q-tile) work items of the
+//      attention kernel -- ceil(n_b * G / 256) per sequence, the heaviest (last) q-tile of a sequence first -- padded
+//      with an empty marker (b = -1) up to the host bound total_tokens * G / 256 + batch_size.  It also raises
+//      SFA_ERR_SEQ_LEN_RANGE for a sequence whose cu_tokens range is not inside [0, total_tokens] or runs backwards.
+//   1. chunk_prologue_kernel<RaggedGeo>: one workgroup per packed row; the row finds its sequence in cu_tokens by
+//      binary search.  The rotated Q goes to the workspace packed over tokens: [Hkv, total_tokens * G, D].
+//   2. chunk_attn_kernel<RaggedGeo>: a 1-D grid of bound * Hkv * S workgroups, workgroup i serving plan item
+//      i / (Hkv * S) and (kv head, split) i % (Hkv * S); it exits on the marker.  The grid follows the token total, not
+//      batch_size * max n_b, and because the plan index is the slow digit every real workgroup is launched before the
+//      first empty one (with the plan index on the fast grid axis the empty slots sat between the real ones and a launch
+//      of about one workgroup per CU ran 1.4x longer: DESIGN.md 5.7).
+//   3. chunk_combine_kernel<RaggedGeo> (num_splits > 1): one thread group per packed query row.
+// Nothing here trusts cu_tokens: every kernel re-derives 0 <= cu[b] <= cu[b+1] <= total_tokens for the sequence it
+// found, a packed row that belongs to no such sequence touches nothing, and plan items past the bound are dropped.
+#include "decode_chunk_body.h"
+
+namespace sfa {
+
+namespace {
+
+using namespace prefill;
+
+// The token range [c0, c1) of sequence b; false when it is empty or not a range inside [0, total).
+__device__ __forceinline__ bool seq_range(const VarlenKernelParams &vp, int b, int &c0, int &c1) {
+    c0 = vp.cu_tokens[b], c1 = vp.cu_tokens[b + 1];
+    return c0 >= 0 && c0 < c1 && c1 <= vp.total;
+}
+
+// The sequence that owns packed row `row` (cu[b] <= row < cu[b+1], a valid range), or -1.  Binary search for the last
+// b with cu[b] <= row; the range check afterwards makes the answer safe for any cu_tokens contents.
+__device__ __forceinline__ int seq_of_row(const VarlenKernelParams &vp, int row, int &c0, int &c1) {
+    int lo = 0, hi = vp.c.d.B;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (vp.cu_tokens[mid] <= row) lo = mid; else hi = mid;
+    }
+    return seq_range(vp, lo, c0, c1) && c0 <= row && row < c1 ? lo : -1;
+}
+
+struct RaggedGeo {
+    using Params = VarlenKernelParams;
+    static __device__ __forceinline__ const ChunkKernelParams &chunk(const Params &vp) { return vp.c; }
+    static __device__ __forceinline__ bool prologue(const Params &vp, int &b, int &t, int &n) {
+        int c0, c1;
+        b = seq_of_row(vp, blockIdx.x, c0, c1);
+        if (b < 0) return false;
+        t = (int)blockIdx.x - c0, n = c1 - c0;
+        return true;
+    }
+    static __device__ __forceinline__ long long qkv_off(const Params &vp, int b, int t) {
+        return (long long)(vp.cu_tokens[b] + t) * vp.c.tok_stride;
+    }
+    // 1-D grid, plan index on the slow digit: every workgroup of every real item is launched before the first empty slot
+    static __device__ __forceinline__ bool attn(const Params &vp, int &b, int &qt, int &hs, int &n, int &R) {
+        const int per_item = vp.c.d.Hkv * vp.c.d.num_splits;
+        hs = (int)(blockIdx.x % per_item);
+        const int2 item = vp.plan[blockIdx.x / per_item];
+        b = item.x, qt = item.y;
+        if (b < 0) return false;                // the empty marker
+        int c0, c1;
+        if (!seq_range(vp, b, c0, c1)) return false;
+        n = c1 - c0, R = n * vp.c.G;            // (n * G <= total * G, an int: checked by sfa_decode_varlen)
+        return qt * kBM < R;
+    }
+    // rotated Q [Hkv, total * G, D] and partials [Hkv, S, total * G, ..]: row cu[b] * G + r of kv head hk
+    static __device__ __forceinline__ long long q_row(const Params &vp, int b, int hk, long long r) {
+        return (long long)hk * vp.rows + (long long)vp.cu_tokens[b] * vp.c.G + r;
+    }
+    static __device__ __forceinline__ long long part_row(const Params &vp, int b, int hk, int split, long long r) {
+        return ((long long)hk * vp.c.d.num_splits + split) * vp.rows + (long long)vp.cu_tokens[b] * vp.c.G + r;
+    }
+    static __device__ __forceinline__ long long o_tok(const Params &vp, int b, int t) { return vp.cu_tokens[b] + t; }
+    static __device__ __forceinline__ bool combine(const Params &vp, long long row, long long &grp, long long &rows,
+                                                   long long &r, long long &tok, int &head) {
+        if (row >= (long long)vp.c.d.Hkv * vp.rows) return false;
+        grp = row / vp.rows, rows = vp.rows, r = row % vp.rows;
+        tok = r / vp.c.G;
+        head = (int)grp * vp.c.G + (int)(r % vp.c.G);
+        int c0, c1;
+        return seq_of_row(vp, (int)tok, c0, c1) >= 0;
+    }
+};
+
+// plan[i] = (b, q_tile) for the i-th work item, (-1, 0) from the last item up to vp.bound.  One workgroup walks the
+// sequences 256 at a time: tile counts, an exclusive scan in LDS, then every thread writes its sequence's items.
+__global__ void __launch_bounds__(256)
+varlen_plan_kernel(const VarlenKernelParams vp) {
+    __shared__ int scan[256];
+    __shared__ int base_s;
+    const int tid = threadIdx.x, B = vp.c.d.B;
+    if (tid == 0) base_s = 0;
+    __syncthreads();
+    for (int b0 = 0; b0 < B; b0 += 256) {
+        const int b = b0 + tid;
+        int tiles = 0;
+        if (b < B) {
+            int c0, c1;
+            if (seq_range(vp, b, c0, c1)) tiles = ((c1 - c0) * vp.c.G + kBM - 1) / kBM;
+            else if (c0 != c1) atomicOr(vp.c.d.status, 1);      // not a range of [0, total): skipped
+        }
+        scan[tid] = tiles;
+        __syncthreads();
+        for (int d = 1; d < 256; d <<= 1) {     // inclusive Hillis-Steele scan
+            const int add = tid >= d ? scan[tid - d] : 0;
+            __syncthreads();
+            scan[tid] += add;
+            __syncthreads();
+        }
+        const int base = base_s;
+        const int first = base + scan[tid] - tiles;
+        for (int i = 0; i < tiles; ++i)
+            if (first + i < vp.bound) vp.plan[first + i] = make_int2(b, tiles - 1 - i);
+        __syncthreads();
+        if (tid == 255) base_s = min(base + scan[255], vp.bound);
+        __syncthreads();
+    }
+    for (int i = base_s + tid; i < vp.bound; i += 256) vp.plan[i] = make_int2(-1, 0);
+}
+
+template <class Tr, int D, bool PAGED>
+int launch_varlen_t(const VarlenKernelParams &vp, hipStream_t stream) {
+    const DecodeKernelParams &p = vp.c.d;
+    hipLaunchKernelGGL(varlen_plan_kernel, dim3(1), dim3(256), 0, stream, vp);
+    if (const int rc = check_launch("varlen_plan_kernel")) return rc;
+
+    hipLaunchKernelGGL((chunk::chunk_prologue_kernel<RaggedGeo, Tr, D, PAGED>), dim3(vp.total), dim3(256), 0, stream, vp);
+    if (const int rc = check_launch("chunk_prologue_kernel<ragged>")) return rc;
+
+    const size_t lds = Lds<D>::TOTAL;
+    static DynLdsAttr attr;
+    if (const int rc = attr.ensure(reinterpret_cast<const void *>(&chunk::chunk_attn_kernel<RaggedGeo, Tr, D, PAGED>),
+                                   (int)lds, "chunk_attn_kernel<ragged>"))
+        return rc;
+    hipLaunchKernelGGL((chunk::chunk_attn_kernel<RaggedGeo, Tr, D, PAGED>),
+                       dim3((unsigned)vp.bound * (unsigned)(p.Hkv * p.num_splits)), dim3(kThreads), lds, stream, vp);
+    if (const int rc = check_launch("chunk_attn_kernel<ragged>")) return rc;
+
+    if (p.num_splits > 1) {
+        const long long threads = (long long)p.Hkv * vp.rows * (D / 8);
+        hipLaunchKernelGGL((chunk::chunk_combine_kernel<RaggedGeo, Tr, D>), dim3((unsigned)((threads + 255) / 256)),
+                           dim3(256), 0, stream, vp);
+        return check_launch("chunk_combine_kernel<ragged>");
+    }
+    return SFA_OK;
+}
+
+template <class Tr, int D>
+int launch_varlen_layout(const VarlenKernelParams &vp, hipStream_t stream) {
+    return vp.c.d.block_table ? launch_varlen_t<Tr, D, true>(vp, stream) : launch_varlen_t<Tr, D, false>(vp, stream);
+}
+
+}  // namespace
+
+int launch_decode_varlen(const VarlenKernelParams &vp, int dtype, int head_dim, hipStream_t stream) {
+    if (dtype == SFA_DTYPE_FP16) {
+        if (head_dim == 128) return launch_varlen_layout<Fp16, 128>(vp, stream);
+        if (head_dim == 64) return launch_varlen_layout<Fp16, 64>(vp, stream);
+    } else if (dtype == SFA_DTYPE_BF16) {
+        if (head_dim == 128) return launch_varlen_layout<Bf16, 128>(vp, stream);
+        if (head_dim == 64) return launch_varlen_layout<Bf16, 64>(vp, stream);
+    } else {
+        return fail(SFA_ERR_BAD_DTYPE, "sfa_decode_varlen: dtype %d is not fp16(0)/bf16(1)", dtype);
+    }
+    return fail(SFA_ERR_UNSUPPORTED_HEAD_DIM, "sfa_decode_varlen: head_dim %d not in {64, 128}", head_dim);
+}
+
+}  // namespace sfa

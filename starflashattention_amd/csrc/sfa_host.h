@@ -38,7 +38,7 @@ struct DecodeKernelParams {
     float scale_log2;       // softmax scale * log2(e)
 };
 
-// sfa_decode_chunk (decode_chunk_kernel.hip): n new tokens per sequence.  Workspace: [0,256) status block,
+// sfa_decode_chunk (decode_chunk_kernel.hip, decode_chunk_body.h): n new tokens per sequence.  Workspace: [0,256) status block,
 // then the rotated Q [B, Hkv, R, D] (16 bit, row r = t*G + g of kv head hk is query head hk*G + g of token t),
 // then (num_splits > 1) fp32 partial outputs [B, Hkv, S, R, D] and float2 (m, l) [B, Hkv, S, R].
 struct ChunkKernelParams {
@@ -48,6 +48,24 @@ struct ChunkKernelParams {
     int n;                  // new tokens per sequence
     int G;                  // query heads per kv head
     int R;                  // query rows per (batch, kv head) = n * G
+};
+
+// sfa_decode_varlen (decode_varlen_kernel.hip): n_b = cu_tokens[b+1] - cu_tokens[b] new tokens for sequence b, packed.
+// With T = total_tokens, G = H / Hkv, rows = T * G, bound = rows / 256 + B (the plan's entries: every sequence with
+// tokens has ceil(n_b * G / 256) <= n_b * G / 256 + 1 q-tiles) and up(x) = x rounded up to 256 bytes, the workspace is
+//   [0, 256)                          status block
+//   up(bound * 8)                     plan: int2 (b, q_tile) per attention workgroup slot, b = -1 = empty
+//   up(Hkv * rows * D * 2)            rotated Q [Hkv, rows, D] (16 bit), row cu_tokens[b] * G + t * G + g
+//   up(Hkv * S * rows * D * 4)        (S > 1) fp32 partial outputs [Hkv, S, rows, D]
+//   up(Hkv * S * rows * 8)            (S > 1) float2 (m, l) [Hkv, S, rows]
+// sfa_decode_varlen_workspace_bytes = the sum: it depends on T, never on how the tokens are spread over sequences.
+struct VarlenKernelParams {
+    ChunkKernelParams c;    // c.n, c.R and c.d.qkv_stride are unused (0): they are per sequence here
+    const int32_t *cu_tokens;   // [B + 1]
+    int2 *plan;             // workspace: [bound]
+    long long rows;         // total * G: packed query rows per kv head
+    int total;              // host bound of cu_tokens[B]: rows of qkv / o
+    int bound;              // plan entries = grid.x of the attention kernel
 };
 
 struct PrefillKernelParams {
@@ -67,6 +85,7 @@ int launch_decode(const DecodeKernelParams &p, int dtype, int head_dim, hipStrea
 int launch_decode_gqa(const DecodeKernelParams &p, int dtype, int head_dim, hipStream_t stream);
 int launch_decode_gqa_mfma(const DecodeKernelParams &p, int dtype, int head_dim, hipStream_t stream);
 int launch_decode_chunk(const ChunkKernelParams &p, int dtype, int head_dim, hipStream_t stream);
+int launch_decode_varlen(const VarlenKernelParams &p, int dtype, int head_dim, hipStream_t stream);
 int launch_prefill(const PrefillKernelParams &p, int dtype, int head_dim, bool causal, hipStream_t stream);
 int launch_prefill_no_keys(const PrefillKernelParams &p, int head_dim, hipStream_t stream);
 int launch_rotary_table(void *cos_t, void *sin_t, int max_seq_len, int rot_dim, int dtype, hipStream_t stream);

@@ -9,6 +9,8 @@ libStarFlashAttention.so.  The public operators:
   flash_attn_fwd(...) prefill forward (new entry point; the reference is decode-only).
   flash_decode_chunk(...)  n new tokens per sequence in one call: prompt ingestion, chunked prefill,
                       speculative verification (new entry point).
+  flash_decode_varlen(...) the same with a token count of its own per sequence, packed: one call for a mixed
+                      prefill / verify / decode step (new entry point).
 """
 import ctypes
 import math
@@ -73,17 +75,18 @@ def release_workspaces():
 
 def _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size, memory_max_len,
                  num_heads, head_dim, rotary_embedding_dim, max_input_length, num_layer, idx_layer, rotary_cos_table,
-                 rotary_sin_table, softmax_scale, kv_layout, block_table, num_heads_kv, tokens=None):
+                 rotary_sin_table, softmax_scale, kv_layout, block_table, num_heads_kv, tokens=None, packed=None):
     """Check the tensors of one decode call and fill its sfa_decode_args, all but the workspace, num_splits and stride.
     tokens None: flash_decode (qkv [B, 3, H, D] or [B, H + 2*Hkv, D], o [B, H, D]); tokens = n: flash_decode_chunk
-    (qkv [B, n, 3, H, D] or [B, n, H + 2*Hkv, D], o [B, n, H, D]).  Returns (args, B, H, Hkv, D, M)."""
+    (qkv [B, n, 3, H, D] or [B, n, H + 2*Hkv, D], o [B, n, H, D]); packed = T: flash_decode_varlen (qkv [T, 3, H, D] or
+    [T, H + 2*Hkv, D], o [T, H, D]: the tokens of all sequences, one after another).  Returns (args, B, H, Hkv, D, M)."""
     _require(isinstance(qkv, torch.Tensor) and qkv.dtype in _DTYPES,
              f"qkv must be a float16 or bfloat16 tensor (got {getattr(qkv, 'dtype', type(qkv))})")
     dt, dev = qkv.dtype, qkv.device
     B, H, D, M, L = int(batch_size), int(num_heads), int(head_dim), int(memory_max_len), int(num_layer)
     Hkv = H if num_heads_kv is None else int(num_heads_kv)
     _require(Hkv > 0 and H % Hkv == 0, f"num_heads={H} must be a multiple of num_heads_kv={Hkv}")
-    lead = (B,) if tokens is None else (B, tokens)
+    lead = (packed,) if packed is not None else (B,) if tokens is None else (B, tokens)
     _check_gpu_tensor(qkv, "qkv", dt, lead + ((3, H, D) if Hkv == H else (H + 2 * Hkv, D)))
     _check_gpu_tensor(o, "o", dt, lead + (H, D), dev)
     _check_gpu_tensor(seq_len, "seq_len", torch.int32, (B,), dev)
@@ -181,7 +184,7 @@ def flash_decode_chunk(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table
     flash_decode and the result of n successive flash_decode calls.  qkv is [B, n, 3, H, D] (grouped queries:
     [B, n, H + 2*num_heads_kv, D]), o is [B, n, H, D]; n = qkv.shape[1].  Token t of sequence b is rotated at and
     appended to position seq_len[b] + t and attends to the cache rows [0, seq_len[b] + t].  seq_len is not
-    incremented.  Ragged prompts: pad to a common n (the rows past a sequence's real length are overwritten by the
+    incremented.  Ragged prompts: flash_decode_varlen, or pad to a common n (the rows past a sequence's real length are overwritten by the
     decode steps that follow, before anything reads them).  Returns `o`."""
     lib = _lib.load()
     _require(isinstance(qkv, torch.Tensor) and qkv.dim() in (4, 5),
@@ -200,6 +203,41 @@ def flash_decode_chunk(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table
         a.workspace = ws.data_ptr()
         a.workspace_bytes = ws.numel()
         _lib.check(lib.sfa_decode_chunk(ctypes.byref(a), n, 0, _stream_ptr(dev)))
+        if _sync_checks:
+            check_decode_status(dev)
+    return o
+
+
+def flash_decode_varlen(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, cu_tokens,
+                        batch_size, memory_max_len, num_heads, head_dim, rotary_embedding_dim,
+                        max_input_length, num_layer, idx_layer, *, num_splits=0,
+                        rotary_cos_table=None, rotary_sin_table=None, softmax_scale=None, kv_layout="blmhd",
+                        block_table=None, num_heads_kv=None):
+    """A ragged batch of new tokens in one call (include/star_flash_attn.h, sfa_decode_varlen): flash_decode_chunk
+    with a token count of its own per sequence.  cu_tokens is an int32 device tensor [B + 1], starting at 0 and
+    non-decreasing; sequence b owns the packed rows [cu_tokens[b], cu_tokens[b+1]) of qkv ([T, 3, H, D]; grouped
+    queries: [T, H + 2*num_heads_kv, D]) and o ([T, H, D]), T = qkv.shape[0] >= cu_tokens[B].  Row cu_tokens[b] + t is
+    rotated at and appended to position seq_len[b] + t and attends to the cache rows [0, seq_len[b] + t]; a sequence
+    with no tokens takes no part, and no cache row past a sequence's own tokens is written.  cu_tokens is only read
+    on the device (no synchronisation; graph replays may change it).  seq_len is not incremented.  Returns `o`."""
+    lib = _lib.load()
+    _require(isinstance(qkv, torch.Tensor) and qkv.dim() in (3, 4),
+             f"qkv must be [T, 3, H, D] or [T, H + 2*Hkv, D] (got {tuple(getattr(qkv, 'shape', ()))})")
+    T = int(qkv.shape[0])
+    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
+                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
+                                      kv_layout, block_table, num_heads_kv, packed=T)
+    dev = qkv.device
+    _check_gpu_tensor(cu_tokens, "cu_tokens", torch.int32, (B + 1,), dev)
+    with torch.cuda.device(dev):
+        S = int(num_splits) if num_splits and num_splits > 0 else 0
+        ws = _workspace(dev, lib.sfa_decode_varlen_workspace_bytes(B, H, Hkv, D, M, T, S))
+        a.stride = 0
+        a.num_splits = S
+        a.workspace = ws.data_ptr()
+        a.workspace_bytes = ws.numel()
+        _lib.check(lib.sfa_decode_varlen(ctypes.byref(a), ctypes.c_void_p(cu_tokens.data_ptr()), T, 0, _stream_ptr(dev)))
         if _sync_checks:
             check_decode_status(dev)
     return o
