@@ -1,7 +1,7 @@
 // extern "C" entry points of libStarFlashAttention.so (declared in include/star_flash_attn.h).
-// Validation + parameter marshalling only; the kernels live in decode_kernel.hip,
-// prefill_kernel.hip and aux_kernels.hip.  Nothing here allocates, copies or synchronises
-// (except sfa_decode_poll_status, which exists to do exactly that).
+// Validation, workspace layout and parameter marshalling only; decode_dispatch.hip and prefill_dispatch.hip pick the
+// kernels, which live in the decode_*_kernel.hip, prefill_*_kernel.hip and aux_kernels.hip files.  Nothing here
+// allocates, copies or synchronises (except sfa_decode_poll_status, which exists to do exactly that).
 #include <climits>
 #include <cmath>
 #include <cstdarg>
@@ -39,26 +39,50 @@ int check_launch(const char *what) {
 
 static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-// Split count when the caller does not choose one (the reference hard-codes 4 with a TODO,
-// flash_api.cpp:38, flash_attn.cu:1024).  Each workgroup is 4 waves on one (b,h,split); aim
-// for >= 4 workgroups per CU (1024 on 256 CUs) but keep >= 256 cached rows per workgroup so
-// every wave still streams >= 64 rows.
-// Split count for num_splits <= 0.  Measured on MI355X (tools/decode_small.py, fp16 D=128): splitting
-// pays only while B*H alone leaves most CUs without a workgroup -- B=1 H=32 M=8192: 72.8 us unsplit,
-// 29.1 us at 4-8 splits, 35.7 at 32; B=2: 74.2 -> 46.8 at 2 splits, 52.0 at 16; from B*H >= 256 on one
-// split is best (the combine kernel and the partials cost ~3 us).  Aim for ~128 workgroups, and keep
-// every split at least 2048 cache rows long.
-static int auto_splits(int B, int H, int /*D*/, int M) {
-    const long long bh = (long long)B * H;
-    long long s = (128 + bh - 1) / bh;
-    const long long cap = M / 2048 > 1 ? M / 2048 : 1;
+DecodeWorkspace decode_workspace(size_t plan_entries, size_t q_rows, size_t part_rows, int S, int D) {
+    DecodeWorkspace w;
+    w.plan = kStatusBytes;
+    w.q_rot = w.plan + align_up(plan_entries * sizeof(int2), 256);
+    w.part_o = w.q_rot + align_up(q_rows * D * sizeof(uint16_t), 256);
+    w.part_ml = w.part_o + align_up(part_rows * S * D * sizeof(float), 256);
+    w.total = S > 1 ? w.part_ml + align_up(part_rows * S * sizeof(float2), 256) : w.part_o;
+    return w;
+}
+
+// Split count when the caller does not choose one (num_splits <= 0; the reference hard-codes 4 with a TODO,
+// flash_api.cpp:38, flash_attn.cu:1024): split the key range only while the unsplit grid of `wgs` workgroups leaves CUs
+// idle -- aim for `target` workgroups, keep every split at least `min_rows` cache rows of memory_max_len long and at
+// most 32 splits.  The count is chosen on the host from memory_max_len; the device splits the actual keys, so a split
+// past a sequence's keys only writes an empty partial.
+static int clamp_splits(long long wgs, long long target, int M, int min_rows) {
+    long long s = (target + wgs - 1) / wgs;
+    const long long cap = M / min_rows > 1 ? M / min_rows : 1;
     if (s > cap) s = cap;
     if (s > 32) s = 32;
     if (s < 1) s = 1;
     return (int)s;
 }
 
-// The kernel parameters of an (already validated) sfa_decode_args, shared by sfa_decode and sfa_decode_chunk; the
+// sfa_decode: one 4-wave workgroup per (b, h, split).  Measured on MI355X (tools/decode_small.py, fp16 D=128): splitting
+// pays only while B*H alone leaves most CUs without a workgroup -- B=1 H=32 M=8192: 72.8 us unsplit, 29.1 us at 4-8
+// splits, 35.7 at 32; B=2: 74.2 -> 46.8 at 2 splits, 52.0 at 16; from B*H >= 256 on one split is best (the combine kernel
+// and the partials cost ~3 us).  Aim for ~128 workgroups, and keep every split at least 2048 cache rows long.
+static int auto_splits(int B, int H, int M) { return clamp_splits((long long)B * H, 128, M, 2048); }
+
+// sfa_decode_chunk: the attention kernel runs one 8-wave workgroup per (batch, kv head, 256-row q-tile, split), one per
+// CU (its LDS): ~256 workgroups, splits of at least 512 cache rows (8 tiles).
+static int chunk_auto_splits(int B, int Hkv, int rows, int M) {
+    return clamp_splits((long long)B * Hkv * ((rows + 255) / 256), 256, M, 512);
+}
+
+// sfa_decode_varlen: the attention grid is bound * Hkv * S workgroups with bound = total_tokens * G / 256 + batch_size
+// plan slots (sfa_host.h); chunk_auto_splits' rule with the workgroup count taken from that bound.
+static int varlen_plan_bound(int B, long long rows) { return (int)(rows / 256 + B); }
+static int varlen_auto_splits(int B, int Hkv, long long rows, int M) {
+    return clamp_splits((long long)varlen_plan_bound(B, rows) * Hkv, 256, M, 512);
+}
+
+// The kernel parameters of an (already validated) sfa_decode_args, shared by the three decode entry points; the
 // callers place part_o / part_ml in the workspace.
 static DecodeKernelParams decode_params(const sfa_decode_args *a, int hkv, int page_shift, int S, long long stride) {
     const long long hd = (long long)hkv * a->head_dim;          // elements per cache row
@@ -104,58 +128,47 @@ static DecodeKernelParams decode_params(const sfa_decode_args *a, int hkv, int p
     return p;
 }
 
-// Split count of sfa_decode_chunk for num_splits <= 0.  The attention kernel runs one 8-wave workgroup per (batch, kv
-// head, 256-row q-tile, split), one per CU (its LDS): split the key range only while B * Hkv * q-tiles leaves CUs
-// idle, aim for ~256 workgroups, keep every split at least 512 cache rows (8 tiles) of memory_max_len long and at
-// most 32 splits.  The split count is chosen on the host from memory_max_len; the device splits the actual
-// seq_len[b] + n keys, so a split past a sequence's keys only writes an empty partial.
-static int splits_for_workgroups(long long wgs, int M) {
-    long long s = (256 + wgs - 1) / wgs;
-    const long long cap = M / 512 > 1 ? M / 512 : 1;
-    if (s > cap) s = cap;
-    if (s > 32) s = 32;
-    if (s < 1) s = 1;
-    return (int)s;
-}
-static int chunk_auto_splits(int B, int Hkv, int rows, int M) {
-    return splits_for_workgroups((long long)B * Hkv * ((rows + 255) / 256), M);
-}
+// What sets the three decode entry points apart in the argument checks they share
+struct EntryPoint {
+    const char *fn;             // names the entry point in the error text
+    const char *count_name;     // its token count: num_tokens per sequence, or, packed, total_tokens over all sequences
+    bool d256;                  // head_dim 256 is served
+    bool token_limits;          // the limits of the chunk kernels: batch_size, 32-bit lane offsets, count * group
+    bool packed;                // the tokens of all sequences are packed: no batch stride
+};
+constexpr EntryPoint kDecode = {"sfa_decode", "num_tokens", true, false, false};
+constexpr EntryPoint kChunk = {"sfa_decode_chunk", "num_tokens", false, true, false};
+constexpr EntryPoint kVarlen = {"sfa_decode_varlen", "total_tokens", false, true, true};
 
-// sfa_decode_varlen: the attention grid is bound * Hkv * S workgroups with bound = total_tokens * G / 256 + batch_size plan slots
-// (sfa_host.h); chunk_auto_splits' rule with the workgroup count taken from that bound.
-static int varlen_plan_bound(int B, long long rows) { return (int)(rows / 256 + B); }
-static int varlen_auto_splits(int B, int Hkv, long long rows, int M) {
-    return splits_for_workgroups((long long)varlen_plan_bound(B, rows) * Hkv, M);
-}
-
-// What sfa_decode_chunk and sfa_decode_varlen check alike, before any HIP call, and what they derive on the way.  FN
-// names the entry point in the error text; COUNT is its token count (COUNT_NAME: num_tokens per sequence, or, PACKED,
-// total_tokens over all sequences).
-struct TokenCall {
+// What the entry points check alike, before any HIP call, and what they derive on the way.  sfa_decode is the case of
+// one token per sequence (count = 1) with no token stride.
+struct DecodeCall {
     int hkv, group, page_shift;
     long long tok, stride;      // elements between tokens / batches of qkv
 };
-static int validate_token_call(const char *fn, const sfa_decode_args *a, const char *count_name, int count, bool packed,
-                               int64_t qkv_token_stride, TokenCall *out) {
+static int validate_decode_call(const EntryPoint &e, const sfa_decode_args *a, int count, int64_t qkv_token_stride,
+                                DecodeCall *out) {
+    const char *fn = e.fn;
     if (!a) return fail(SFA_ERR_NULL_POINTER, "%s: args is NULL", fn);
     if (!a->qkv || !a->o || !a->seq_len || !a->k_cache_table || !a->v_cache_table)
         return fail(SFA_ERR_NULL_POINTER, "%s: qkv/o/seq_len/k_cache_table/v_cache_table must be non-NULL", fn);
     if ((a->rotary_cos_table == nullptr) != (a->rotary_sin_table == nullptr))
         return fail(SFA_ERR_NULL_POINTER, "%s: give both rotary tables or neither", fn);
-    if (count < 0) return fail(SFA_ERR_BAD_SHAPE, "%s: %s=%d < 0", fn, count_name, count);
-    if (a->batch_size < 0 || a->batch_size > 65535 || a->num_heads <= 0 || a->memory_max_len <= 0 || a->num_layer <= 0)
-        return fail(SFA_ERR_BAD_SHAPE,
-                    "%s: batch_size=%d (<= 65535) num_heads=%d memory_max_len=%d num_layer=%d", fn,
-                    a->batch_size, a->num_heads, a->memory_max_len, a->num_layer);
+    if (count < 0) return fail(SFA_ERR_BAD_SHAPE, "%s: %s=%d < 0", fn, e.count_name, count);
+    if (a->batch_size < 0 || (e.token_limits && a->batch_size > 65535) || a->num_heads <= 0 || a->memory_max_len <= 0 ||
+        a->num_layer <= 0)
+        return fail(SFA_ERR_BAD_SHAPE, "%s: batch_size=%d%s num_heads=%d memory_max_len=%d num_layer=%d", fn,
+                    a->batch_size, e.token_limits ? " (<= 65535)" : "", a->num_heads, a->memory_max_len, a->num_layer);
     if (a->idx_layer < 0 || a->idx_layer >= a->num_layer)
         return fail(SFA_ERR_BAD_SHAPE, "%s: idx_layer=%d outside [0, num_layer=%d)", fn, a->idx_layer,
                     a->num_layer);
-    if (a->head_dim == 256)
+    if (a->head_dim == 256 && !e.d256)
         return fail(SFA_ERR_UNSUPPORTED_HEAD_DIM,
                     "%s: head_dim 256 is not supported by the chunk path yet (64 or 128; sfa_decode "
                     "serves 256 one token at a time)", fn);
-    if (a->head_dim != 64 && a->head_dim != 128)
-        return fail(SFA_ERR_UNSUPPORTED_HEAD_DIM, "%s: head_dim %d not in {64, 128}", fn, a->head_dim);
+    if (a->head_dim != 64 && a->head_dim != 128 && a->head_dim != 256)
+        return fail(SFA_ERR_UNSUPPORTED_HEAD_DIM, "%s: head_dim %d not in {64, 128%s}", fn, a->head_dim,
+                    e.d256 ? ", 256" : "");
     if (a->rotary_embedding_dim < 0 || a->rotary_embedding_dim > a->head_dim || (a->rotary_embedding_dim & 1))
         return fail(SFA_ERR_BAD_SHAPE, "%s: rotary_embedding_dim=%d must be even and in [0, head_dim]", fn,
                     a->rotary_embedding_dim);
@@ -172,7 +185,7 @@ static int validate_token_call(const char *fn, const sfa_decode_args *a, const c
     if (tok < row || (tok % 8) != 0)
         return fail(SFA_ERR_BAD_SHAPE,
                     "%s: qkv_token_stride %lld must be >= (H + 2*Hkv)*D and a multiple of 8", fn, tok);
-    if (packed && a->stride != 0)
+    if (e.packed && a->stride != 0)
         return fail(SFA_ERR_BAD_SHAPE, "%s: args->stride=%d must be 0 (the tokens of all sequences are packed)", fn,
                     a->stride);
     const long long stride = a->stride > 0 ? a->stride : (long long)count * tok;
@@ -181,8 +194,8 @@ static int validate_token_call(const char *fn, const sfa_decode_args *a, const c
                     "%s: qkv stride %lld must be >= (num_tokens-1)*token_stride + (H + 2*Hkv)*D and a "
                     "multiple of 8", fn, stride);
     // (packed: the plan kernel sums up to 256 sequences' q-tiles of garbage cu_tokens in an int)
-    if ((long long)count * group > (packed ? INT_MAX / 2 : INT_MAX))
-        return fail(SFA_ERR_BAD_SHAPE, "%s: %s * group = %lld query rows per kv head is too many", fn, count_name,
+    if (e.token_limits && (long long)count * group > (e.packed ? INT_MAX / 2 : INT_MAX))
+        return fail(SFA_ERR_BAD_SHAPE, "%s: %s * group = %lld query rows per kv head is too many", fn, e.count_name,
                     (long long)count * group);
     if (a->num_splits > 1024)
         return fail(SFA_ERR_BAD_SHAPE, "%s: num_splits=%d > 1024", fn, a->num_splits);
@@ -190,7 +203,7 @@ static int validate_token_call(const char *fn, const sfa_decode_args *a, const c
         return fail(SFA_ERR_BAD_SHAPE,
                     "%s: kv_layout %d is not SFA_KV_BLMHD(0)/SFA_KV_BLHMD(1)/SFA_KV_PAGED(2)", fn, a->kv_layout);
     // the attention kernel addresses the 64 rows of a tile with 32-bit lane offsets
-    if (a->kv_layout != SFA_KV_BLHMD && 128ll * hkv * a->head_dim >= (1ll << 31))
+    if (e.token_limits && a->kv_layout != SFA_KV_BLHMD && 128ll * hkv * a->head_dim >= (1ll << 31))
         return fail(SFA_ERR_BAD_SHAPE, "%s: num_heads_kv * head_dim = %lld too large", fn,
                     (long long)hkv * a->head_dim);
     int page_shift = 0;
@@ -212,6 +225,15 @@ static int validate_token_call(const char *fn, const sfa_decode_args *a, const c
     if (align_or & 15) return fail(SFA_ERR_BAD_SHAPE, "%s: tensors must be 16-byte aligned", fn);
     out->hkv = hkv, out->group = group, out->page_shift = page_shift;
     out->tok = tok, out->stride = stride;
+    return SFA_OK;
+}
+
+// The workspace an entry point was given holds `need` bytes at a 256-byte boundary
+static int check_workspace(const EntryPoint &e, const sfa_decode_args *a, size_t need) {
+    if (!a->workspace) return fail(SFA_ERR_NULL_POINTER, "%s: workspace is NULL (need %zu bytes)", e.fn, need);
+    if (a->workspace_bytes < need)
+        return fail(SFA_ERR_WORKSPACE_TOO_SMALL, "%s: workspace has %zu bytes, need %zu", e.fn, a->workspace_bytes, need);
+    if ((uintptr_t)a->workspace & 255) return fail(SFA_ERR_BAD_SHAPE, "%s: workspace must be 256-byte aligned", e.fn);
     return SFA_OK;
 }
 
@@ -268,28 +290,22 @@ int sfa_debug_get(const char *knob) {
     return INT_MIN;
 }
 
-int sfa_decode_auto_splits(int batch_size, int num_heads, int head_dim, int memory_max_len) {
+int sfa_decode_auto_splits(int batch_size, int num_heads, int /*head_dim*/, int memory_max_len) {
     if (batch_size <= 0 || num_heads <= 0 || memory_max_len <= 0) return 1;
-    return auto_splits(batch_size, num_heads, head_dim, memory_max_len);
+    return auto_splits(batch_size, num_heads, memory_max_len);
 }
 
 size_t sfa_decode_workspace_bytes(int batch_size, int num_heads, int head_dim, int memory_max_len,
                                   int num_splits) {
     if (batch_size <= 0 || num_heads <= 0 || head_dim <= 0) return kStatusBytes;
-    const int S = num_splits > 0 ? num_splits : auto_splits(batch_size, num_heads, head_dim, memory_max_len);
-    size_t bytes = kStatusBytes;
-    if (S > 1) {
-        const size_t bhs = (size_t)batch_size * num_heads * S;
-        bytes += align_up(bhs * head_dim * sizeof(float), 256);
-        bytes += align_up(bhs * sizeof(float2), 256);
-    }
-    return bytes;
+    const int S = num_splits > 0 ? num_splits : auto_splits(batch_size, num_heads, memory_max_len);
+    return decode_workspace(0, 0, (size_t)batch_size * num_heads, S, head_dim).total;
 }
 
 size_t sfa_decode_workspace_bytes_gqa(int batch_size, int num_heads, int num_heads_kv, int head_dim, int memory_max_len,
                                       int num_splits) {
     const int hkv = num_heads_kv > 0 ? num_heads_kv : num_heads;
-    const int S = num_splits > 0 ? num_splits : auto_splits(batch_size, hkv, head_dim, memory_max_len);
+    const int S = num_splits > 0 ? num_splits : auto_splits(batch_size, hkv, memory_max_len);
     return sfa_decode_workspace_bytes(batch_size, num_heads, head_dim, memory_max_len, S);
 }
 
@@ -318,195 +334,116 @@ int sfa_decode_poll_status(const void *workspace, void *stream) {
 }
 
 int sfa_decode(const sfa_decode_args *a, void *stream) {
-    if (!a) return fail(SFA_ERR_NULL_POINTER, "sfa_decode: args is NULL");
-    if (!a->qkv || !a->o || !a->seq_len || !a->k_cache_table || !a->v_cache_table)
-        return fail(SFA_ERR_NULL_POINTER, "sfa_decode: qkv/o/seq_len/k_cache_table/v_cache_table must be non-NULL");
-    if ((a->rotary_cos_table == nullptr) != (a->rotary_sin_table == nullptr))
-        return fail(SFA_ERR_NULL_POINTER, "sfa_decode: give both rotary tables or neither");
-    if (a->batch_size < 0 || a->num_heads <= 0 || a->memory_max_len <= 0 || a->num_layer <= 0)
-        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode: batch_size=%d num_heads=%d memory_max_len=%d num_layer=%d",
-                    a->batch_size, a->num_heads, a->memory_max_len, a->num_layer);
-    if (a->idx_layer < 0 || a->idx_layer >= a->num_layer)
-        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode: idx_layer=%d outside [0, num_layer=%d)", a->idx_layer, a->num_layer);
-    if (a->head_dim != 64 && a->head_dim != 128 && a->head_dim != 256)
-        return fail(SFA_ERR_UNSUPPORTED_HEAD_DIM, "sfa_decode: head_dim %d not in {64, 128, 256}", a->head_dim);
-    if (a->rotary_embedding_dim < 0 || a->rotary_embedding_dim > a->head_dim || (a->rotary_embedding_dim & 1))
-        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode: rotary_embedding_dim=%d must be even and in [0, head_dim]",
-                    a->rotary_embedding_dim);
-    if (a->dtype != SFA_DTYPE_FP16 && a->dtype != SFA_DTYPE_BF16)
-        return fail(SFA_ERR_BAD_DTYPE, "sfa_decode: dtype %d is not fp16(0)/bf16(1)", a->dtype);
-    const int hkv = a->num_heads_kv > 0 ? a->num_heads_kv : a->num_heads;
-    const int group = hkv > 0 ? a->num_heads / hkv : 0;
-    if (a->num_heads_kv < 0 || group * hkv != a->num_heads ||
-        (group != 1 && group != 2 && group != 4 && group != 8 && group != 16))
-        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode: num_heads=%d / num_heads_kv=%d must be 1, 2, 4, 8 or 16",
-                    a->num_heads, a->num_heads_kv);
-    const long long row = (long long)(a->num_heads + 2 * hkv) * a->head_dim;    // packed q,k,v of one token
-    const long long stride = a->stride > 0 ? a->stride : row;
-    if (stride < row || (stride % 8) != 0)
-        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode: qkv stride %lld must be >= (H + 2*Hkv)*D and a multiple of 8", stride);
-    if (a->num_splits > 1024)
-        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode: num_splits=%d > 1024", a->num_splits);
-    if (a->kv_layout != SFA_KV_BLMHD && a->kv_layout != SFA_KV_BLHMD && a->kv_layout != SFA_KV_PAGED)
-        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode: kv_layout %d is not SFA_KV_BLMHD(0)/SFA_KV_BLHMD(1)/SFA_KV_PAGED(2)",
-                    a->kv_layout);
-    int page_shift = 0;
-    if (a->kv_layout == SFA_KV_PAGED) {
-        if (!a->block_table) return fail(SFA_ERR_NULL_POINTER, "sfa_decode: kv_layout PAGED needs block_table");
-        if (a->page_size < 16 || (a->page_size & (a->page_size - 1)))
-            return fail(SFA_ERR_BAD_SHAPE, "sfa_decode: page_size=%d must be a power of two >= 16", a->page_size);
-        while ((1 << page_shift) < a->page_size) ++page_shift;
-        if (a->num_pages <= 0 ||
-            (long long)a->block_table_stride * a->page_size < (long long)a->memory_max_len)
-            return fail(SFA_ERR_BAD_SHAPE,
-                        "sfa_decode: num_pages=%d, block_table_stride=%d * page_size=%d must cover memory_max_len=%d",
-                        a->num_pages, a->block_table_stride, a->page_size, a->memory_max_len);
-        if ((uintptr_t)a->block_table & 3) return fail(SFA_ERR_BAD_SHAPE, "sfa_decode: block_table must be 4-byte aligned");
-    }
-    const uintptr_t align_or = (uintptr_t)a->qkv | (uintptr_t)a->o | (uintptr_t)a->k_cache_table |
-                               (uintptr_t)a->v_cache_table | (uintptr_t)a->q_bias | (uintptr_t)a->k_bias |
-                               (uintptr_t)a->v_bias;
-    if (align_or & 15) return fail(SFA_ERR_BAD_SHAPE, "sfa_decode: tensors must be 16-byte aligned");
+    DecodeCall dc;
+    if (const int rc = validate_decode_call(kDecode, a, 1, 0, &dc)) return rc;
     if (a->batch_size == 0) return SFA_OK;
 
+    const size_t bh = (size_t)a->batch_size * a->num_heads;
     // grouped queries launch one workgroup per KV head: the split count follows the kv-head count
-    int S = a->num_splits > 0
-                ? a->num_splits
-                : auto_splits(a->batch_size, hkv, a->head_dim, a->memory_max_len);
+    int S = a->num_splits > 0 ? a->num_splits : auto_splits(a->batch_size, dc.hkv, a->memory_max_len);
     // A caller that left the choice to the library sized its workspace with sfa_decode_workspace_bytes(..., 0), which
     // knows the query-head count only: with grouped queries the library's own choice can be larger than the one that
     // size was computed for.  Take the largest split count the workspace holds rather than fail.
     if (a->num_splits <= 0 && a->workspace)
-        while (S > 1 && a->workspace_bytes < sfa_decode_workspace_bytes(a->batch_size, a->num_heads, a->head_dim,
-                                                                         a->memory_max_len, S))
-            --S;
-    const size_t need = sfa_decode_workspace_bytes(a->batch_size, a->num_heads, a->head_dim,
-                                                   a->memory_max_len, S);
-    if (!a->workspace) return fail(SFA_ERR_NULL_POINTER, "sfa_decode: workspace is NULL (need %zu bytes)", need);
-    if (a->workspace_bytes < need)
-        return fail(SFA_ERR_WORKSPACE_TOO_SMALL, "sfa_decode: workspace has %zu bytes, need %zu",
-                    a->workspace_bytes, need);
-    if ((uintptr_t)a->workspace & 255)
-        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode: workspace must be 256-byte aligned");
+        while (S > 1 && a->workspace_bytes < decode_workspace(0, 0, bh, S, a->head_dim).total) --S;
+    const DecodeWorkspace w = decode_workspace(0, 0, bh, S, a->head_dim);
+    if (const int rc = check_workspace(kDecode, a, w.total)) return rc;
 
-    DecodeKernelParams p = decode_params(a, hkv, page_shift, S, stride);
+    DecodeKernelParams p = decode_params(a, dc.hkv, dc.page_shift, S, dc.stride);
     char *ws = (char *)a->workspace;
-    const size_t bhs = (size_t)a->batch_size * a->num_heads * S;
-    p.part_o = (float *)(ws + kStatusBytes);
-    p.part_ml = (float2 *)(ws + kStatusBytes + align_up(bhs * a->head_dim * sizeof(float), 256));
+    p.part_o = (float *)(ws + w.part_o);
+    p.part_ml = (float2 *)(ws + w.part_ml);
     return launch_decode(p, a->dtype, a->head_dim, (hipStream_t)stream);
+}
+
+// (query rows per (batch, kv head) = num_tokens * group; bhr of them in all)
+static DecodeWorkspace chunk_workspace(int B, int hkv, long long rows, int S, int D) {
+    const size_t bhr = (size_t)B * hkv * rows;
+    return decode_workspace(0, bhr, bhr, S, D);
 }
 
 size_t sfa_decode_chunk_workspace_bytes(int batch_size, int num_heads, int num_heads_kv, int head_dim,
                                         int memory_max_len, int num_tokens, int num_splits) {
     if (batch_size <= 0 || num_heads <= 0 || head_dim <= 0 || num_tokens <= 0) return kStatusBytes;
     const int hkv = num_heads_kv > 0 ? num_heads_kv : num_heads;
-    const long long rows = (long long)num_tokens * (num_heads / hkv);     // query rows per (batch, kv head)
+    const long long rows = (long long)num_tokens * (num_heads / hkv);
     const int S = num_splits > 0 ? num_splits
                                  : chunk_auto_splits(batch_size, hkv, (int)(rows < INT_MAX ? rows : INT_MAX), memory_max_len);
-    const size_t bhr = (size_t)batch_size * hkv * rows;
-    size_t bytes = kStatusBytes + align_up(bhr * head_dim * sizeof(uint16_t), 256);     // rotated Q
-    if (S > 1) {
-        bytes += align_up(bhr * S * head_dim * sizeof(float), 256);
-        bytes += align_up(bhr * S * sizeof(float2), 256);
-    }
-    return bytes;
+    return chunk_workspace(batch_size, hkv, rows, S, head_dim).total;
 }
 
 int sfa_decode_chunk(const sfa_decode_args *a, int num_tokens, int64_t qkv_token_stride, void *stream) {
-    TokenCall tc;
-    if (const int rc = validate_token_call("sfa_decode_chunk", a, "num_tokens", num_tokens, false, qkv_token_stride, &tc))
-        return rc;
+    DecodeCall dc;
+    if (const int rc = validate_decode_call(kChunk, a, num_tokens, qkv_token_stride, &dc)) return rc;
     if (a->batch_size == 0 || num_tokens == 0) return SFA_OK;
-    const int hkv = tc.hkv, group = tc.group;
 
-    const int rows = num_tokens * group;
-    const int S = a->num_splits > 0 ? a->num_splits : chunk_auto_splits(a->batch_size, hkv, rows, a->memory_max_len);
-    const size_t need = sfa_decode_chunk_workspace_bytes(a->batch_size, a->num_heads, hkv, a->head_dim,
-                                                         a->memory_max_len, num_tokens, S);
-    if (!a->workspace) return fail(SFA_ERR_NULL_POINTER, "sfa_decode_chunk: workspace is NULL (need %zu bytes)", need);
-    if (a->workspace_bytes < need)
-        return fail(SFA_ERR_WORKSPACE_TOO_SMALL, "sfa_decode_chunk: workspace has %zu bytes, need %zu",
-                    a->workspace_bytes, need);
-    if ((uintptr_t)a->workspace & 255)
-        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk: workspace must be 256-byte aligned");
+    const int rows = num_tokens * dc.group;
+    const int S = a->num_splits > 0 ? a->num_splits : chunk_auto_splits(a->batch_size, dc.hkv, rows, a->memory_max_len);
+    const DecodeWorkspace w = chunk_workspace(a->batch_size, dc.hkv, rows, S, a->head_dim);
+    if (const int rc = check_workspace(kChunk, a, w.total)) return rc;
 
     ChunkKernelParams p;
     memset(&p, 0, sizeof(p));
-    p.d = decode_params(a, hkv, tc.page_shift, S, tc.stride);
+    p.d = decode_params(a, dc.hkv, dc.page_shift, S, dc.stride);
     char *ws = (char *)a->workspace;
-    const size_t bhr = (size_t)a->batch_size * hkv * rows;
-    const size_t q_bytes = align_up(bhr * a->head_dim * sizeof(uint16_t), 256);
-    p.q_rot = (uint16_t *)(ws + kStatusBytes);
-    p.d.part_o = (float *)(ws + kStatusBytes + q_bytes);
-    p.d.part_ml = (float2 *)(ws + kStatusBytes + q_bytes + align_up(bhr * S * a->head_dim * sizeof(float), 256));
-    p.tok_stride = tc.tok;
+    p.q_rot = (uint16_t *)(ws + w.q_rot);
+    p.d.part_o = (float *)(ws + w.part_o);
+    p.d.part_ml = (float2 *)(ws + w.part_ml);
+    p.tok_stride = dc.tok;
     p.n = num_tokens;
-    p.G = group;
+    p.G = dc.group;
     p.R = rows;
     return launch_decode_chunk(p, a->dtype, a->head_dim, (hipStream_t)stream);
+}
+
+// (rows = total_tokens * group packed query rows per kv head)
+static DecodeWorkspace varlen_workspace(int B, int hkv, long long rows, int S, int D) {
+    const size_t hr = (size_t)hkv * rows;
+    return decode_workspace((size_t)varlen_plan_bound(B, rows), hr, hr, S, D);
 }
 
 size_t sfa_decode_varlen_workspace_bytes(int batch_size, int num_heads, int num_heads_kv, int head_dim,
                                          int memory_max_len, int total_tokens, int num_splits) {
     if (batch_size <= 0 || num_heads <= 0 || head_dim <= 0 || total_tokens <= 0) return kStatusBytes;
     const int hkv = num_heads_kv > 0 ? num_heads_kv : num_heads;
-    const long long rows = (long long)total_tokens * (num_heads / hkv);     // packed query rows per kv head
+    const long long rows = (long long)total_tokens * (num_heads / hkv);
     const int S = num_splits > 0 ? num_splits : varlen_auto_splits(batch_size, hkv, rows, memory_max_len);
-    const size_t hr = (size_t)hkv * rows;
-    size_t bytes = kStatusBytes + align_up((size_t)varlen_plan_bound(batch_size, rows) * sizeof(int2), 256);    // plan
-    bytes += align_up(hr * head_dim * sizeof(uint16_t), 256);               // rotated Q
-    if (S > 1) {
-        bytes += align_up(hr * S * head_dim * sizeof(float), 256);
-        bytes += align_up(hr * S * sizeof(float2), 256);
-    }
-    return bytes;
+    return varlen_workspace(batch_size, hkv, rows, S, head_dim).total;
 }
 
 int sfa_decode_varlen(const sfa_decode_args *a, const void *cu_tokens, int total_tokens, int64_t qkv_token_stride,
                       void *stream) {
-    TokenCall tc;
+    DecodeCall dc;
     if (a && !cu_tokens) return fail(SFA_ERR_NULL_POINTER, "sfa_decode_varlen: cu_tokens is NULL");
-    if (const int rc = validate_token_call("sfa_decode_varlen", a, "total_tokens", total_tokens, true, qkv_token_stride,
-                                           &tc))
-        return rc;
+    if (const int rc = validate_decode_call(kVarlen, a, total_tokens, qkv_token_stride, &dc)) return rc;
     if ((uintptr_t)cu_tokens & 3) return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_varlen: cu_tokens must be 4-byte aligned");
-    const long long rows = (long long)total_tokens * tc.group;
+    const long long rows = (long long)total_tokens * dc.group;
     if (a->batch_size == 0 || total_tokens == 0) return SFA_OK;
 
-    const int hkv = tc.hkv;
+    const int hkv = dc.hkv, bound = varlen_plan_bound(a->batch_size, rows);
     const int S = a->num_splits > 0 ? a->num_splits : varlen_auto_splits(a->batch_size, hkv, rows, a->memory_max_len);
     // the attention kernel's 1-D grid: one workgroup per (plan slot, kv head, split)
-    if ((long long)varlen_plan_bound(a->batch_size, rows) * hkv * S > INT_MAX)
+    if ((long long)bound * hkv * S > INT_MAX)
         return fail(SFA_ERR_BAD_SHAPE,
                     "sfa_decode_varlen: total_tokens=%d, batch_size=%d, num_heads_kv=%d and num_splits=%d need more than "
                     "2^31 - 1 attention workgroups", total_tokens, a->batch_size, hkv, S);
-    const size_t need = sfa_decode_varlen_workspace_bytes(a->batch_size, a->num_heads, hkv, a->head_dim,
-                                                          a->memory_max_len, total_tokens, S);
-    if (!a->workspace) return fail(SFA_ERR_NULL_POINTER, "sfa_decode_varlen: workspace is NULL (need %zu bytes)", need);
-    if (a->workspace_bytes < need)
-        return fail(SFA_ERR_WORKSPACE_TOO_SMALL, "sfa_decode_varlen: workspace has %zu bytes, need %zu",
-                    a->workspace_bytes, need);
-    if ((uintptr_t)a->workspace & 255)
-        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_varlen: workspace must be 256-byte aligned");
+    const DecodeWorkspace w = varlen_workspace(a->batch_size, hkv, rows, S, a->head_dim);
+    if (const int rc = check_workspace(kVarlen, a, w.total)) return rc;
 
     VarlenKernelParams p;
     memset(&p, 0, sizeof(p));
-    p.c.d = decode_params(a, hkv, tc.page_shift, S, 0);
-    p.c.tok_stride = tc.tok;
-    p.c.G = tc.group;
+    p.c.d = decode_params(a, hkv, dc.page_shift, S, 0);
+    p.c.tok_stride = dc.tok;
+    p.c.G = dc.group;
     p.cu_tokens = (const int32_t *)cu_tokens;
     p.rows = rows;
     p.total = total_tokens;
-    p.bound = varlen_plan_bound(a->batch_size, rows);
-    char *ws = (char *)a->workspace + kStatusBytes;     // the layout of sfa_host.h
-    const size_t hr = (size_t)hkv * rows;
-    p.plan = (int2 *)ws;
-    ws += align_up((size_t)p.bound * sizeof(int2), 256);
-    p.c.q_rot = (uint16_t *)ws;
-    ws += align_up(hr * a->head_dim * sizeof(uint16_t), 256);
-    p.c.d.part_o = (float *)ws;
-    p.c.d.part_ml = (float2 *)(ws + align_up(hr * S * a->head_dim * sizeof(float), 256));
+    p.bound = bound;
+    char *ws = (char *)a->workspace;
+    p.plan = (int2 *)(ws + w.plan);
+    p.c.q_rot = (uint16_t *)(ws + w.q_rot);
+    p.c.d.part_o = (float *)(ws + w.part_o);
+    p.c.d.part_ml = (float2 *)(ws + w.part_ml);
     return launch_decode_varlen(p, a->dtype, a->head_dim, (hipStream_t)stream);
 }
 

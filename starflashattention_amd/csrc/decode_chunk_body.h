@@ -431,5 +431,41 @@ chunk_combine_kernel(const typename GEO::Params gp) {
     *reinterpret_cast<uint4 *>(orow + sub * 8) = pack8<Tr>(y);
 }
 
+// Host side.  The launches of one call, ordered by the stream alone: prologue, attention, and (num_splits > 1) the
+// combine over combine_rows rows of the rotated Q.  The caller has the grids of its geometry.
+template <class GEO, class Tr, int D, bool PAGED>
+int launch_chunk_t(const typename GEO::Params &gp, int num_splits, dim3 prologue_grid, dim3 attn_grid, long long combine_rows,
+                   hipStream_t stream) {
+    hipLaunchKernelGGL((chunk_prologue_kernel<GEO, Tr, D, PAGED>), prologue_grid, dim3(256), 0, stream, gp);
+    if (const int rc = check_launch("chunk_prologue_kernel")) return rc;
+
+    const size_t lds = Lds<D>::TOTAL;          // K[3] + V[3], padded rows
+    static DynLdsAttr attr;
+    if (const int rc = attr.ensure(reinterpret_cast<const void *>(&chunk_attn_kernel<GEO, Tr, D, PAGED>), (int)lds,
+                                   "chunk_attn_kernel"))
+        return rc;
+    hipLaunchKernelGGL((chunk_attn_kernel<GEO, Tr, D, PAGED>), attn_grid, dim3(kThreads), lds, stream, gp);
+    if (const int rc = check_launch("chunk_attn_kernel")) return rc;
+
+    if (num_splits > 1) {
+        const long long threads = combine_rows * (D / 8);
+        hipLaunchKernelGGL((chunk_combine_kernel<GEO, Tr, D>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, gp);
+        return check_launch("chunk_combine_kernel");
+    }
+    return SFA_OK;
+}
+
+// The instantiation for a validated call: fp16 / bf16, head_dim 64 / 128; p is the call's DecodeKernelParams
+template <class GEO, class... Grids>
+int launch_chunk(const typename GEO::Params &gp, const DecodeKernelParams &p, int dtype, int head_dim, Grids... grids) {
+    const bool h = dtype == SFA_DTYPE_FP16, paged = p.block_table != nullptr;
+    if (head_dim == 64) {
+        if (paged) return h ? launch_chunk_t<GEO, Fp16, 64, true>(gp, p.num_splits, grids...) : launch_chunk_t<GEO, Bf16, 64, true>(gp, p.num_splits, grids...);
+        return h ? launch_chunk_t<GEO, Fp16, 64, false>(gp, p.num_splits, grids...) : launch_chunk_t<GEO, Bf16, 64, false>(gp, p.num_splits, grids...);
+    }
+    if (paged) return h ? launch_chunk_t<GEO, Fp16, 128, true>(gp, p.num_splits, grids...) : launch_chunk_t<GEO, Bf16, 128, true>(gp, p.num_splits, grids...);
+    return h ? launch_chunk_t<GEO, Fp16, 128, false>(gp, p.num_splits, grids...) : launch_chunk_t<GEO, Bf16, 128, false>(gp, p.num_splits, grids...);
+}
+
 }  // namespace chunk
 }  // namespace sfa

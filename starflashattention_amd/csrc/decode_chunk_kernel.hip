@@ -17,7 +17,7 @@
 //   3. chunk_combine_kernel (num_splits > 1 only): merges the partials, as decode_combine_kernel does.  A split
 //      that lies past a row's causal limit left (m = -inf, l = 0) for it, which the merge ignores.
 // The kernels themselves are in decode_chunk_body.h, shared with the ragged sfa_decode_varlen; this file holds the
-// uniform geometry (UniformGeo) and the launches.
+// uniform geometry (UniformGeo) and its grids.
 // Rejection (decode_chunk_common.h, reject_code): every kernel re-derives it from seq_len / block_table; the
 // prologue raises the sticky status bit and touches no cache row, the attention kernel writes NaN outputs.
 // A block_table entry outside the pool on a page that is only READ is replaced by page 0, raises bit 2 and turns
@@ -68,48 +68,13 @@ struct UniformGeo {
     }
 };
 
-template <class Tr, int D, bool PAGED>
-int launch_chunk_t(const ChunkKernelParams &p, hipStream_t stream) {
-    hipLaunchKernelGGL((chunk::chunk_prologue_kernel<UniformGeo, Tr, D, PAGED>), dim3(p.n, p.d.B), dim3(256), 0, stream, p);
-    if (const int rc = check_launch("chunk_prologue_kernel")) return rc;
-
-    const size_t lds = Lds<D>::TOTAL;          // K[3] + V[3], padded rows
-    static DynLdsAttr attr;
-    if (const int rc = attr.ensure(reinterpret_cast<const void *>(&chunk::chunk_attn_kernel<UniformGeo, Tr, D, PAGED>), (int)lds,
-                                   "chunk_attn_kernel"))
-        return rc;
-    const int row_tiles = (p.R + kBM - 1) / kBM;
-    hipLaunchKernelGGL((chunk::chunk_attn_kernel<UniformGeo, Tr, D, PAGED>), dim3(row_tiles, p.d.Hkv * p.d.num_splits, p.d.B),
-                       dim3(kThreads), lds, stream, p);
-    if (const int rc = check_launch("chunk_attn_kernel")) return rc;
-
-    if (p.d.num_splits > 1) {
-        const long long threads = (long long)p.d.B * p.d.Hkv * p.R * (D / 8);
-        hipLaunchKernelGGL((chunk::chunk_combine_kernel<UniformGeo, Tr, D>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
-                           stream, p);
-        return check_launch("chunk_combine_kernel");
-    }
-    return SFA_OK;
-}
-
-template <class Tr, int D>
-int launch_chunk_layout(const ChunkKernelParams &p, hipStream_t stream) {
-    return p.d.block_table ? launch_chunk_t<Tr, D, true>(p, stream) : launch_chunk_t<Tr, D, false>(p, stream);
-}
-
 }  // namespace
 
 int launch_decode_chunk(const ChunkKernelParams &p, int dtype, int head_dim, hipStream_t stream) {
-    if (dtype == SFA_DTYPE_FP16) {
-        if (head_dim == 128) return launch_chunk_layout<Fp16, 128>(p, stream);
-        if (head_dim == 64) return launch_chunk_layout<Fp16, 64>(p, stream);
-    } else if (dtype == SFA_DTYPE_BF16) {
-        if (head_dim == 128) return launch_chunk_layout<Bf16, 128>(p, stream);
-        if (head_dim == 64) return launch_chunk_layout<Bf16, 64>(p, stream);
-    } else {
-        return fail(SFA_ERR_BAD_DTYPE, "sfa_decode_chunk: dtype %d is not fp16(0)/bf16(1)", dtype);
-    }
-    return fail(SFA_ERR_UNSUPPORTED_HEAD_DIM, "sfa_decode_chunk: head_dim %d not in {64, 128}", head_dim);
+    const int row_tiles = (p.R + kBM - 1) / kBM;
+    return chunk::launch_chunk<UniformGeo>(p, p.d, dtype, head_dim, dim3(p.n, p.d.B),
+                                           dim3(row_tiles, p.d.Hkv * p.d.num_splits, p.d.B),
+                                           (long long)p.d.B * p.d.Hkv * p.R, stream);
 }
 
 }  // namespace sfa

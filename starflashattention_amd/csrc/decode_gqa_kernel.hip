@@ -10,8 +10,8 @@
 //
 // Per cached row and lane the work is G x (4 v_dot2 + 4 DPP adds + softmax update + 8 FMA): at G = 4
 // the VALU is about as busy as HBM, at G = 8 the kernel is VALU-bound -- still far cheaper than
-// streaming the cache 8 times.  K/V loads use the non-temporal policy under the same rule as
-// decode_kernel.hip.
+// streaming the cache 8 times.  decode_dispatch.hip chooses between this kernel and the matrix-core one and decides
+// the K/V load policy (NT).
 #include <cstdlib>
 
 #include "decode_common.h"
@@ -278,10 +278,8 @@ decode_gqa_kernel(const DecodeKernelParams p) {
 }
 
 template <class Tr, int D, int G>
-int launch_g(const DecodeKernelParams &p, hipStream_t stream) {
+int launch_g(const DecodeKernelParams &p, bool nt, hipStream_t stream) {
     dim3 grid(p.Hkv, p.num_splits, p.B), block(kDecodeWaves * 64);
-    bool nt = 4ll * p.B * p.L * p.M * p.Hkv * D > (256ll << 20);       // see decode_kernel.hip
-    if (const int k = g_knobs.decode_nt.load(std::memory_order_relaxed); k >= 0) nt = k != 0;      // tests, A/B
     if (p.block_table) {
         if (nt) hipLaunchKernelGGL((decode_gqa_kernel<Tr, D, G, true, true>), grid, block, 0, stream, p);
         else hipLaunchKernelGGL((decode_gqa_kernel<Tr, D, G, false, true>), grid, block, 0, stream, p);
@@ -293,40 +291,24 @@ int launch_g(const DecodeKernelParams &p, hipStream_t stream) {
 }
 
 template <class Tr, int D>
-int launch_t(const DecodeKernelParams &p, hipStream_t stream) {
-    switch (p.H / p.Hkv) {
-        case 2: return launch_g<Tr, D, 2>(p, stream);
-        case 4: return launch_g<Tr, D, 4>(p, stream);
-        case 8: return launch_g<Tr, D, 8>(p, stream);
-        default: return fail(SFA_ERR_BAD_SHAPE, "sfa_decode: num_heads / num_heads_kv = %d not in {1, 2, 4, 8}", p.H / p.Hkv);
-    }
+int launch_t(const DecodeKernelParams &p, bool nt, hipStream_t stream) {
+    if (p.H == 2 * p.Hkv) return launch_g<Tr, D, 2>(p, nt, stream);
+    if (p.H == 4 * p.Hkv) return launch_g<Tr, D, 4>(p, nt, stream);
+    return launch_g<Tr, D, 8>(p, nt, stream);
 }
 
 }  // namespace
 
-// the attention kernel only; launch_decode (decode_kernel.hip) adds the split combine
-int launch_decode_gqa(const DecodeKernelParams &p, int dtype, int head_dim, hipStream_t stream) {
-    // 8 query heads per kv head make this kernel VALU-bound (4.1 TB/s at head_dim 128): the matrix-core form takes
-    // over -- for groups of 16 always, for 8 at any head_dim, for 4 at head_dim 128 (measured there); 
-    // sfa_debug_set("decode_gqa_mfma", 0) keeps the VALU kernel for A/B, 1 forces the matrix-core kernel for groups of 4
-    if ((head_dim == 128 || head_dim == 64 || head_dim == 256) && (p.H == 16 * p.Hkv || p.H == 8 * p.Hkv || p.H == 4 * p.Hkv) &&
-        (dtype == SFA_DTYPE_FP16 || dtype == SFA_DTYPE_BF16)) {
-        const int knob = g_knobs.decode_gqa_mfma.load(std::memory_order_relaxed);
-        const bool by_default = head_dim == 128 || p.H >= 8 * p.Hkv;
-        if (p.H == 16 * p.Hkv || (knob < 0 ? by_default : knob != 0)) return launch_decode_gqa_mfma(p, dtype, head_dim, stream);
-    }
+// 2, 4 or 8 query heads per kv head: one workgroup per (batch, kv head, split) serves the whole group
+int launch_decode_gqa(const DecodeKernelParams &p, int dtype, int head_dim, bool nt, hipStream_t stream) {
     if (dtype == SFA_DTYPE_FP16) {
-        if (head_dim == 128) return launch_t<Fp16, 128>(p, stream);
-        if (head_dim == 256) return launch_t<Fp16, 256>(p, stream);
-        if (head_dim == 64) return launch_t<Fp16, 64>(p, stream);
-    } else if (dtype == SFA_DTYPE_BF16) {
-        if (head_dim == 128) return launch_t<Bf16, 128>(p, stream);
-        if (head_dim == 256) return launch_t<Bf16, 256>(p, stream);
-        if (head_dim == 64) return launch_t<Bf16, 64>(p, stream);
-    } else {
-        return fail(SFA_ERR_BAD_DTYPE, "sfa_decode: dtype %d is not fp16(0)/bf16(1)", dtype);
+        if (head_dim == 128) return launch_t<Fp16, 128>(p, nt, stream);
+        if (head_dim == 256) return launch_t<Fp16, 256>(p, nt, stream);
+        return launch_t<Fp16, 64>(p, nt, stream);
     }
-    return fail(SFA_ERR_UNSUPPORTED_HEAD_DIM, "sfa_decode: head_dim %d not in {64, 128, 256}", head_dim);
+    if (head_dim == 128) return launch_t<Bf16, 128>(p, nt, stream);
+    if (head_dim == 256) return launch_t<Bf16, 256>(p, nt, stream);
+    return launch_t<Bf16, 64>(p, nt, stream);
 }
 
 }  // namespace sfa

@@ -405,9 +405,7 @@ int launch_k(const DecodeKernelParams &p, hipStream_t stream) {
 }
 
 template <class Tr, int D, int G>
-int launch_g(const DecodeKernelParams &p, hipStream_t stream) {
-    bool nt = 4ll * p.B * p.L * p.M * p.Hkv * D > (256ll << 20);        // see decode_kernel.hip
-    if (const int k = g_knobs.decode_nt.load(std::memory_order_relaxed); k >= 0) nt = k != 0;      // tests, A/B
+int launch_g(const DecodeKernelParams &p, bool nt, hipStream_t stream) {
     // Reference layout: a K row of this head is a 256-B segment H*D*2 bytes from the next, and fetching it
     // as 64-B operand pieces costs 8 % (5.96 vs 6.44 TB/s): load row-major, re-lay out through LDS.
     // Head-major caches are contiguous, the operand-layout loads go straight to registers (6.7 TB/s).
@@ -419,20 +417,20 @@ int launch_g(const DecodeKernelParams &p, hipStream_t stream) {
 }
 
 template <class Tr, int D>
-int launch_d(const DecodeKernelParams &p, hipStream_t stream) {
-    if (p.H == 16 * p.Hkv) return launch_g<Tr, D, 16>(p, stream);
-    if (p.H == 4 * p.Hkv) return launch_g<Tr, D, 4>(p, stream);
-    return launch_g<Tr, D, 8>(p, stream);
+int launch_d(const DecodeKernelParams &p, bool nt, hipStream_t stream) {
+    if (p.H == 16 * p.Hkv) return launch_g<Tr, D, 16>(p, nt, stream);
+    if (p.H == 4 * p.Hkv) return launch_g<Tr, D, 4>(p, nt, stream);
+    return launch_g<Tr, D, 8>(p, nt, stream);
 }
 
 }  // namespace
 
 // head_dim 64 / 128 / 256, any cache layout, 4, 8 or 16 query heads per kv head
-int launch_decode_gqa_mfma(const DecodeKernelParams &p, int dtype, int head_dim, hipStream_t stream) {
+int launch_decode_gqa_mfma(const DecodeKernelParams &p, int dtype, int head_dim, bool nt, hipStream_t stream) {
     const bool h = dtype == SFA_DTYPE_FP16;
-    if (head_dim == 64) return h ? launch_d<Fp16, 64>(p, stream) : launch_d<Bf16, 64>(p, stream);
-    if (head_dim == 256) return h ? launch_d<Fp16, 256>(p, stream) : launch_d<Bf16, 256>(p, stream);
-    return h ? launch_d<Fp16, 128>(p, stream) : launch_d<Bf16, 128>(p, stream);
+    if (head_dim == 64) return h ? launch_d<Fp16, 64>(p, nt, stream) : launch_d<Bf16, 64>(p, nt, stream);
+    if (head_dim == 256) return h ? launch_d<Fp16, 256>(p, nt, stream) : launch_d<Bf16, 256>(p, nt, stream);
+    return h ? launch_d<Fp16, 128>(p, nt, stream) : launch_d<Bf16, 128>(p, nt, stream);
 }
 
 }  // namespace sfa

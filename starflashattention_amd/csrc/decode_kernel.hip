@@ -306,56 +306,51 @@ decode_combine_kernel(const DecodeKernelParams p) {
     *reinterpret_cast<uint4 *>(p.o + bh * D + sub * 8) = pack8<Tr>(y);
 }
 
+// the attention kernel, or (combine) the merge of its partials
 template <class Tr, int D>
-int launch_decode_t(const DecodeKernelParams &p, int dtype, hipStream_t stream) {
-    int rc;
-    if (p.Hkv != p.H) {
-        // grouped queries: one workgroup per (batch, kv head, split) serves the whole group
-        rc = launch_decode_gqa(p, dtype, D, stream);
-    } else {
-        dim3 grid(p.H, p.num_splits, p.B), block(kDecodeWaves * 64);
-        // The cache rows are read exactly once per call.  When the two caches together do not fit the
-        // 256 MB Infinity Cache nothing of them survives until the next token's call either, so they are
-        // loaded non-temporally (config 4: 6.30 -> 6.51 TB/s); a small cache keeps the default policy
-        // and is re-read from the Infinity Cache / L2.  sfa_debug_set("decode_nt", 0/1) overrides (tests, A/B).
-        bool nt = 4ll * p.B * p.L * p.M * p.H * D > (256ll << 20);
-        if (const int k = g_knobs.decode_nt.load(std::memory_order_relaxed); k >= 0) nt = k != 0;      // tests, A/B
-        if (p.block_table) {
-            // a step of at most 16 rows touches at most two pages (page_size >= 16)
-            constexpr int UP = (16 / (64 / (D / 8))) < 4 ? (16 / (64 / (D / 8))) : 4;
-            if (nt) hipLaunchKernelGGL((decode_kernel<Tr, D, UP, true, true>), grid, block, 0, stream, p);
-            else hipLaunchKernelGGL((decode_kernel<Tr, D, UP, false, true>), grid, block, 0, stream, p);
-        } else {
-            if (nt) hipLaunchKernelGGL((decode_kernel<Tr, D, 4, true>), grid, block, 0, stream, p);
-            else hipLaunchKernelGGL((decode_kernel<Tr, D, 4, false>), grid, block, 0, stream, p);
-        }
-        rc = check_launch("decode_kernel");
-    }
-    if (rc != SFA_OK) return rc;
-    if (p.num_splits > 1) {
+int launch_t(const DecodeKernelParams &p, bool combine, bool nt, hipStream_t stream) {
+    if (combine) {
         const long long threads = (long long)p.B * p.H * (D / 8);
         dim3 g2((unsigned)((threads + 255) / 256)), b2(256);
         hipLaunchKernelGGL((decode_combine_kernel<Tr, D>), g2, b2, 0, stream, p);
-        rc = check_launch("decode_combine_kernel");
+        return check_launch("decode_combine_kernel");
     }
-    return rc;
+    dim3 grid(p.H, p.num_splits, p.B), block(kDecodeWaves * 64);
+    if (p.block_table) {
+        // a step of at most 16 rows touches at most two pages (page_size >= 16)
+        constexpr int UP = (16 / (64 / (D / 8))) < 4 ? (16 / (64 / (D / 8))) : 4;
+        if (nt) hipLaunchKernelGGL((decode_kernel<Tr, D, UP, true, true>), grid, block, 0, stream, p);
+        else hipLaunchKernelGGL((decode_kernel<Tr, D, UP, false, true>), grid, block, 0, stream, p);
+    } else {
+        if (nt) hipLaunchKernelGGL((decode_kernel<Tr, D, 4, true>), grid, block, 0, stream, p);
+        else hipLaunchKernelGGL((decode_kernel<Tr, D, 4, false>), grid, block, 0, stream, p);
+    }
+    return check_launch("decode_kernel");
+}
+
+// (one fan-out for both: the kernels of a <Tr, D> are instantiated next to each other, and the compiler's inlining of the
+// device helpers they share follows the order of the kernels in the module)
+int launch(const DecodeKernelParams &p, int dtype, int head_dim, bool combine, bool nt, hipStream_t stream) {
+    if (dtype == SFA_DTYPE_FP16) {
+        if (head_dim == 128) return launch_t<Fp16, 128>(p, combine, nt, stream);
+        if (head_dim == 256) return launch_t<Fp16, 256>(p, combine, nt, stream);
+        return launch_t<Fp16, 64>(p, combine, nt, stream);
+    }
+    if (head_dim == 128) return launch_t<Bf16, 128>(p, combine, nt, stream);
+    if (head_dim == 256) return launch_t<Bf16, 256>(p, combine, nt, stream);
+    return launch_t<Bf16, 64>(p, combine, nt, stream);
 }
 
 }  // namespace
 
-int launch_decode(const DecodeKernelParams &p, int dtype, int head_dim, hipStream_t stream) {
-    if (dtype == SFA_DTYPE_FP16) {
-        if (head_dim == 128) return launch_decode_t<Fp16, 128>(p, dtype, stream);
-        if (head_dim == 256) return launch_decode_t<Fp16, 256>(p, dtype, stream);
-        if (head_dim == 64) return launch_decode_t<Fp16, 64>(p, dtype, stream);
-    } else if (dtype == SFA_DTYPE_BF16) {
-        if (head_dim == 128) return launch_decode_t<Bf16, 128>(p, dtype, stream);
-        if (head_dim == 256) return launch_decode_t<Bf16, 256>(p, dtype, stream);
-        if (head_dim == 64) return launch_decode_t<Bf16, 64>(p, dtype, stream);
-    } else {
-        return fail(SFA_ERR_BAD_DTYPE, "sfa_decode: dtype %d is not fp16(0)/bf16(1)", dtype);
-    }
-    return fail(SFA_ERR_UNSUPPORTED_HEAD_DIM, "sfa_decode: head_dim %d not in {64, 128, 256}", head_dim);
+// one query head per kv head: one workgroup per (batch, head, split)
+int launch_decode_mha(const DecodeKernelParams &p, int dtype, int head_dim, bool nt, hipStream_t stream) {
+    return launch(p, dtype, head_dim, false, nt, stream);
+}
+
+// merges the partials of any of the three attention kernels (num_splits > 1)
+int launch_decode_combine(const DecodeKernelParams &p, int dtype, int head_dim, hipStream_t stream) {
+    return launch(p, dtype, head_dim, true, false, stream);
 }
 
 }  // namespace sfa

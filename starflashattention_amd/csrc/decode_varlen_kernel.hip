@@ -124,51 +124,15 @@ varlen_plan_kernel(const VarlenKernelParams vp) {
     for (int i = base_s + tid; i < vp.bound; i += 256) vp.plan[i] = make_int2(-1, 0);
 }
 
-template <class Tr, int D, bool PAGED>
-int launch_varlen_t(const VarlenKernelParams &vp, hipStream_t stream) {
-    const DecodeKernelParams &p = vp.c.d;
-    hipLaunchKernelGGL(varlen_plan_kernel, dim3(1), dim3(256), 0, stream, vp);
-    if (const int rc = check_launch("varlen_plan_kernel")) return rc;
-
-    hipLaunchKernelGGL((chunk::chunk_prologue_kernel<RaggedGeo, Tr, D, PAGED>), dim3(vp.total), dim3(256), 0, stream, vp);
-    if (const int rc = check_launch("chunk_prologue_kernel<ragged>")) return rc;
-
-    const size_t lds = Lds<D>::TOTAL;
-    static DynLdsAttr attr;
-    if (const int rc = attr.ensure(reinterpret_cast<const void *>(&chunk::chunk_attn_kernel<RaggedGeo, Tr, D, PAGED>),
-                                   (int)lds, "chunk_attn_kernel<ragged>"))
-        return rc;
-    hipLaunchKernelGGL((chunk::chunk_attn_kernel<RaggedGeo, Tr, D, PAGED>),
-                       dim3((unsigned)vp.bound * (unsigned)(p.Hkv * p.num_splits)), dim3(kThreads), lds, stream, vp);
-    if (const int rc = check_launch("chunk_attn_kernel<ragged>")) return rc;
-
-    if (p.num_splits > 1) {
-        const long long threads = (long long)p.Hkv * vp.rows * (D / 8);
-        hipLaunchKernelGGL((chunk::chunk_combine_kernel<RaggedGeo, Tr, D>), dim3((unsigned)((threads + 255) / 256)),
-                           dim3(256), 0, stream, vp);
-        return check_launch("chunk_combine_kernel<ragged>");
-    }
-    return SFA_OK;
-}
-
-template <class Tr, int D>
-int launch_varlen_layout(const VarlenKernelParams &vp, hipStream_t stream) {
-    return vp.c.d.block_table ? launch_varlen_t<Tr, D, true>(vp, stream) : launch_varlen_t<Tr, D, false>(vp, stream);
-}
-
 }  // namespace
 
 int launch_decode_varlen(const VarlenKernelParams &vp, int dtype, int head_dim, hipStream_t stream) {
-    if (dtype == SFA_DTYPE_FP16) {
-        if (head_dim == 128) return launch_varlen_layout<Fp16, 128>(vp, stream);
-        if (head_dim == 64) return launch_varlen_layout<Fp16, 64>(vp, stream);
-    } else if (dtype == SFA_DTYPE_BF16) {
-        if (head_dim == 128) return launch_varlen_layout<Bf16, 128>(vp, stream);
-        if (head_dim == 64) return launch_varlen_layout<Bf16, 64>(vp, stream);
-    } else {
-        return fail(SFA_ERR_BAD_DTYPE, "sfa_decode_varlen: dtype %d is not fp16(0)/bf16(1)", dtype);
-    }
-    return fail(SFA_ERR_UNSUPPORTED_HEAD_DIM, "sfa_decode_varlen: head_dim %d not in {64, 128}", head_dim);
+    const DecodeKernelParams &p = vp.c.d;
+    hipLaunchKernelGGL(varlen_plan_kernel, dim3(1), dim3(256), 0, stream, vp);
+    if (const int rc = check_launch("varlen_plan_kernel")) return rc;
+    return chunk::launch_chunk<RaggedGeo>(vp, p, dtype, head_dim, dim3(vp.total),
+                                          dim3((unsigned)vp.bound * (unsigned)(p.Hkv * p.num_splits)),
+                                          (long long)p.Hkv * vp.rows, stream);
 }
 
 }  // namespace sfa

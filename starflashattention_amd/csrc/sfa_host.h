@@ -14,9 +14,23 @@ namespace sfa {
 void set_error(const char *fmt, ...);
 int fail(int status, const char *fmt, ...);
 
-// Workspace layout of sfa_decode: [0,256) status block, then fp32 partial outputs
-// [B,H,S,D], then float2 (m, l) [B,H,S].
 constexpr size_t kStatusBytes = 256;
+
+// The workspace of sfa_decode, sfa_decode_chunk and sfa_decode_varlen: byte offsets of its regions, in this order, each
+// rounded up to 256 bytes (a region an entry point does not have is empty), and the size the caller must provide.
+//   [0, 256)   status block (sticky error word)
+//   plan       int2 (b, q_tile) per attention workgroup slot, b = -1 = empty.  varlen only: bound = rows / 256 + B entries
+//              (every sequence with tokens has ceil(n_b * G / 256) <= n_b * G / 256 + 1 q-tiles)
+//   q_rot      rotated Q, 16 bit.  chunk: [B, Hkv, R, D], row r = t*G + g of kv head hk is query head hk*G + g of token
+//              t; varlen: [Hkv, rows, D], row cu_tokens[b] * G + t * G + g, rows = total_tokens * G
+//   part_o     (S > 1) fp32 partial outputs.  decode: [B, H, S, D]; chunk: [B, Hkv, S, R, D]; varlen: [Hkv, S, rows, D]
+//   part_ml    (S > 1) float2 (m, l), the same index without D
+// The sizes depend on the token total, never on how the tokens are spread over sequences.
+struct DecodeWorkspace {
+    size_t plan, q_rot, part_o, part_ml, total;
+};
+// q_rows rows of rotated Q (0: sfa_decode), part_rows * S rows of partials
+DecodeWorkspace decode_workspace(size_t plan_entries, size_t q_rows, size_t part_rows, int S, int D);
 
 struct DecodeKernelParams {
     const uint16_t *qkv;
@@ -38,9 +52,7 @@ struct DecodeKernelParams {
     float scale_log2;       // softmax scale * log2(e)
 };
 
-// sfa_decode_chunk (decode_chunk_kernel.hip, decode_chunk_body.h): n new tokens per sequence.  Workspace: [0,256) status block,
-// then the rotated Q [B, Hkv, R, D] (16 bit, row r = t*G + g of kv head hk is query head hk*G + g of token t),
-// then (num_splits > 1) fp32 partial outputs [B, Hkv, S, R, D] and float2 (m, l) [B, Hkv, S, R].
+// sfa_decode_chunk (decode_chunk_kernel.hip, decode_chunk_body.h): n new tokens per sequence.
 struct ChunkKernelParams {
     DecodeKernelParams d;   // every field keeps its sfa_decode meaning; d.part_o / d.part_ml are the chunk partials
     uint16_t *q_rot;        // workspace: rotated, rounded Q
@@ -51,14 +63,6 @@ struct ChunkKernelParams {
 };
 
 // sfa_decode_varlen (decode_varlen_kernel.hip): n_b = cu_tokens[b+1] - cu_tokens[b] new tokens for sequence b, packed.
-// With T = total_tokens, G = H / Hkv, rows = T * G, bound = rows / 256 + B (the plan's entries: every sequence with
-// tokens has ceil(n_b * G / 256) <= n_b * G / 256 + 1 q-tiles) and up(x) = x rounded up to 256 bytes, the workspace is
-//   [0, 256)                          status block
-//   up(bound * 8)                     plan: int2 (b, q_tile) per attention workgroup slot, b = -1 = empty
-//   up(Hkv * rows * D * 2)            rotated Q [Hkv, rows, D] (16 bit), row cu_tokens[b] * G + t * G + g
-//   up(Hkv * S * rows * D * 4)        (S > 1) fp32 partial outputs [Hkv, S, rows, D]
-//   up(Hkv * S * rows * 8)            (S > 1) float2 (m, l) [Hkv, S, rows]
-// sfa_decode_varlen_workspace_bytes = the sum: it depends on T, never on how the tokens are spread over sequences.
 struct VarlenKernelParams {
     ChunkKernelParams c;    // c.n, c.R and c.d.qkv_stride are unused (0): they are per sequence here
     const int32_t *cu_tokens;   // [B + 1]
@@ -81,9 +85,13 @@ struct PrefillKernelParams {
     int fast_scale;         // caller allows the prescaled-Q flavour (only used when lse == nullptr)
 };
 
-int launch_decode(const DecodeKernelParams &p, int dtype, int head_dim, hipStream_t stream);
-int launch_decode_gqa(const DecodeKernelParams &p, int dtype, int head_dim, hipStream_t stream);
-int launch_decode_gqa_mfma(const DecodeKernelParams &p, int dtype, int head_dim, hipStream_t stream);
+int launch_decode(const DecodeKernelParams &p, int dtype, int head_dim, hipStream_t stream);     // decode_dispatch.hip
+// the attention kernels launch_decode chooses from (validated dtype / head_dim; nt: non-temporal cache loads) and the
+// split combine
+int launch_decode_mha(const DecodeKernelParams &p, int dtype, int head_dim, bool nt, hipStream_t stream);
+int launch_decode_gqa(const DecodeKernelParams &p, int dtype, int head_dim, bool nt, hipStream_t stream);
+int launch_decode_gqa_mfma(const DecodeKernelParams &p, int dtype, int head_dim, bool nt, hipStream_t stream);
+int launch_decode_combine(const DecodeKernelParams &p, int dtype, int head_dim, hipStream_t stream);
 int launch_decode_chunk(const ChunkKernelParams &p, int dtype, int head_dim, hipStream_t stream);
 int launch_decode_varlen(const VarlenKernelParams &p, int dtype, int head_dim, hipStream_t stream);
 int launch_prefill(const PrefillKernelParams &p, int dtype, int head_dim, bool causal, hipStream_t stream);
@@ -98,8 +106,8 @@ int check_launch(const char *what);
 struct DebugKnobs {
     std::atomic<int> prefill_impl{-1};      // prefill_dispatch.hip: which prefill kernel (PrefillImpl, prefill_common.h)
     std::atomic<int> prefill_pairs{-1};     // prefill_kernel.hip: balanced q-tile pairs per workgroup (1 or 2)
-    std::atomic<int> decode_nt{-1};         // decode kernels: 0 / 1 force default / non-temporal cache loads
-    std::atomic<int> decode_gqa_mfma{-1};   // decode_gqa_kernel.hip: 0 forces the VALU grouped-query kernel
+    std::atomic<int> decode_nt{-1};         // decode_dispatch.hip: 0 / 1 force default / non-temporal cache loads
+    std::atomic<int> decode_gqa_mfma{-1};   // decode_dispatch.hip: 0 forces the VALU grouped-query kernel
     std::atomic<int> bm128_one_wg{-1};      // prefill_kernel_bm128.hip: 1 = one workgroup per CU (A/B library only)
     std::atomic<int> last_prefill_kernel{-1};   // written by launch_prefill: what ran last (sfa_debug_get)
 };

@@ -138,6 +138,18 @@ def _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_
     return a, B, H, Hkv, D, M
 
 
+def _call_decode(dev, a, stride, num_splits, ws, call):
+    """What the three decode operators end in: the batch stride, the split count and the workspace go into `a`,
+    call(args, stream) makes the C-ABI call and, with sync checks on, the status is polled."""
+    a.stride = stride
+    a.num_splits = num_splits
+    a.workspace = ws.data_ptr()
+    a.workspace_bytes = ws.numel()
+    _lib.check(call(ctypes.byref(a), _stream_ptr(dev)))
+    if _sync_checks:
+        check_decode_status(dev)
+
+
 def flash_decode(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o,
                  batch_size, memory_max_len, num_heads, head_dim, rotary_embedding_dim,
                  max_input_length, num_layer, idx_layer, *, num_splits=0, _sized_by_query_heads=False,
@@ -165,13 +177,7 @@ def flash_decode(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_
             S = 0
             ws = torch.empty(lib.sfa_decode_workspace_bytes(B, H, D, M, 0), dtype=torch.uint8, device=dev)
             _lib.check(lib.sfa_decode_reset_status(ctypes.c_void_p(ws.data_ptr()), _stream_ptr(dev)))
-        a.stride = (H + 2 * Hkv) * D
-        a.num_splits = S
-        a.workspace = ws.data_ptr()
-        a.workspace_bytes = ws.numel()
-        _lib.check(lib.sfa_decode(ctypes.byref(a), _stream_ptr(dev)))
-        if _sync_checks:
-            check_decode_status(dev)
+        _call_decode(dev, a, (H + 2 * Hkv) * D, S, ws, lib.sfa_decode)
     return o
 
 
@@ -198,13 +204,8 @@ def flash_decode_chunk(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table
     with torch.cuda.device(dev):
         S = int(num_splits) if num_splits and num_splits > 0 else 0
         ws = _workspace(dev, lib.sfa_decode_chunk_workspace_bytes(B, H, Hkv, D, M, n, S))
-        a.stride = 0                        # n * (H + 2*Hkv) * D, computed by the library in 64 bit
-        a.num_splits = S
-        a.workspace = ws.data_ptr()
-        a.workspace_bytes = ws.numel()
-        _lib.check(lib.sfa_decode_chunk(ctypes.byref(a), n, 0, _stream_ptr(dev)))
-        if _sync_checks:
-            check_decode_status(dev)
+        # (stride 0: n * (H + 2*Hkv) * D, computed by the library in 64 bit)
+        _call_decode(dev, a, 0, S, ws, lambda args, stream: lib.sfa_decode_chunk(args, n, 0, stream))
     return o
 
 
@@ -233,13 +234,8 @@ def flash_decode_varlen(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_tabl
     with torch.cuda.device(dev):
         S = int(num_splits) if num_splits and num_splits > 0 else 0
         ws = _workspace(dev, lib.sfa_decode_varlen_workspace_bytes(B, H, Hkv, D, M, T, S))
-        a.stride = 0
-        a.num_splits = S
-        a.workspace = ws.data_ptr()
-        a.workspace_bytes = ws.numel()
-        _lib.check(lib.sfa_decode_varlen(ctypes.byref(a), ctypes.c_void_p(cu_tokens.data_ptr()), T, 0, _stream_ptr(dev)))
-        if _sync_checks:
-            check_decode_status(dev)
+        cu = ctypes.c_void_p(cu_tokens.data_ptr())
+        _call_decode(dev, a, 0, S, ws, lambda args, stream: lib.sfa_decode_varlen(args, cu, T, 0, stream))
     return o
 
 

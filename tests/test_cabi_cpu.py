@@ -148,6 +148,149 @@ def test_auto_splits_and_workspace(lib):
     assert lib.sfa_decode_workspace_bytes_gqa(2, 32, 32, 128, 8192, 0) == lib.sfa_decode_workspace_bytes(2, 32, 128, 8192, 0)
 
 
+def _up(x):
+    return (x + 255) // 256 * 256
+
+
+def test_decode_workspace_bytes_closed_formula(lib):
+    """sfa_decode_workspace_bytes = 256 + up(B*H*S*D*4) + up(B*H*S*8) for S > 1 and 256 for S = 1, at shapes whose
+    (m, l) term is not a multiple of 256 (a row of partial outputs, D * 4 bytes, always is)."""
+    ws = lib.sfa_decode_workspace_bytes
+    for B, H, D, S in ((3, 5, 64, 3), (1, 3, 128, 5), (7, 1, 256, 9)):
+        assert (B * H * S * 8) % 256
+        assert ws(B, H, D, 4096, S) == 256 + _up(B * H * S * D * 4) + _up(B * H * S * 8), (B, H, D, S)
+        assert ws(B, H, D, 4096, 1) == 256
+        for M in (4096, 65536):
+            assert ws(B, H, D, M, 0) == ws(B, H, D, M, lib.sfa_decode_auto_splits(B, H, D, M)), (B, H, D, M)
+    assert lib.sfa_decode_auto_splits(3, 5, 64, 65536) > 1         # the num_splits = 0 sizes above include partials
+
+
+ENTRY_POINTS = ("sfa_decode", "sfa_decode_chunk", "sfa_decode_varlen")
+_ROW = (8 + 2 * 4) * 128        # (H + 2*Hkv) * D of the well-formed call below
+
+
+def _well_formed():
+    """A call every entry point accepts up to its workspace check (the workspace is NULL): 4 tokens, 8 query heads in
+    groups of 2, head_dim 128, fake 16-byte aligned pointers."""
+    a = _lib.DecodeArgs()
+    for f in ("qkv", "o", "seq_len", "k_cache_table", "v_cache_table"):
+        setattr(a, f, 0x1000)
+    a.batch_size, a.num_heads, a.num_heads_kv, a.memory_max_len, a.num_layer, a.head_dim = 1, 8, 4, 64, 1, 128
+    a.rotary_embedding_dim = 128
+    return a, {"count": 4, "token_stride": 0, "cu_tokens": 0x4000, "null_args": False}
+
+
+def _set(**fields):
+    def mutate(a, call, entry):
+        for k, v in fields.items():
+            if k in call:
+                call[k] = v
+            else:
+                setattr(a, k, v)
+    return mutate
+
+
+def _paged(**fields):
+    return _set(kv_layout=_lib.KV_LAYOUTS["paged"], **{**dict(block_table=0x3000, page_size=16, num_pages=4,
+                                                               block_table_stride=4), **fields})
+
+
+def _workspace(short=0, address=0x2000):
+    """A workspace for num_splits = 3 at `address`, `short` bytes smaller than the entry point asks for."""
+    def mutate(a, call, entry):
+        lib = _lib.load()
+        need = {"sfa_decode": lambda: lib.sfa_decode_workspace_bytes(1, 8, 128, 64, 3),
+                "sfa_decode_chunk": lambda: lib.sfa_decode_chunk_workspace_bytes(1, 8, 4, 128, 64, 4, 3),
+                "sfa_decode_varlen": lambda: lib.sfa_decode_varlen_workspace_bytes(1, 8, 4, 128, 64, 4, 3)}[entry]()
+        a.num_splits, a.workspace, a.workspace_bytes = 3, address, need - short
+    return mutate
+
+
+def _malformed_status(lib, entry, mutate):
+    a, call = _well_formed()
+    mutate(a, call, entry)
+    args = None if call["null_args"] else ctypes.byref(a)
+    if entry == "sfa_decode":
+        st = lib.sfa_decode(args, None)
+    elif entry == "sfa_decode_chunk":
+        st = lib.sfa_decode_chunk(args, call["count"], call["token_stride"], None)
+    else:
+        st = lib.sfa_decode_varlen(args, call["cu_tokens"], call["count"], call["token_stride"], None)
+    return st, lib.sfa_last_error()
+
+
+# (what is wrong, how the well-formed call is changed, the status of sfa_decode / sfa_decode_chunk / sfa_decode_varlen).
+# WS: the entry point has nothing to object to and goes on to its workspace check, which fails with -1 "workspace is
+# NULL"; a plain -1 is another NULL pointer.  The codes were recorded from the library as it was when sfa_decode and the
+# token calls each had a validator of their own.
+WS = "workspace is NULL"
+MALFORMED = [
+    ("nothing: the workspace check", _set(), (WS, WS, WS)),
+    ("NULL args", _set(null_args=True), (-1, -1, -1)),
+    ("qkv missing", _set(qkv=None), (-1, -1, -1)),
+    ("o missing", _set(o=None), (-1, -1, -1)),
+    ("seq_len missing", _set(seq_len=None), (-1, -1, -1)),
+    ("k_cache_table missing", _set(k_cache_table=None), (-1, -1, -1)),
+    ("v_cache_table missing", _set(v_cache_table=None), (-1, -1, -1)),
+    ("cu_tokens missing", _set(cu_tokens=None), (WS, WS, -1)),
+    ("cos table only", _set(rotary_cos_table=0x5000), (-1, -1, -1)),
+    ("sin table only", _set(rotary_sin_table=0x5000), (-1, -1, -1)),
+    ("negative count", _set(count=-1), (WS, -2, -2)),
+    ("negative batch_size", _set(batch_size=-1), (-2, -2, -2)),
+    ("batch_size 65536", _set(batch_size=65536), (WS, -2, -2)),
+    ("num_heads 0", _set(num_heads=0), (-2, -2, -2)),
+    ("memory_max_len 0", _set(memory_max_len=0), (-2, -2, -2)),
+    ("idx_layer = num_layer", _set(idx_layer=1), (-2, -2, -2)),
+    ("idx_layer negative", _set(idx_layer=-1), (-2, -2, -2)),
+    ("head_dim 96", _set(head_dim=96), (-4, -4, -4)),
+    ("head_dim 256", _set(head_dim=256, rotary_embedding_dim=0), (WS, -4, -4)),
+    ("odd rotary_embedding_dim", _set(rotary_embedding_dim=127), (-2, -2, -2)),
+    ("rotary_embedding_dim > head_dim", _set(rotary_embedding_dim=130), (-2, -2, -2)),
+    ("dtype 7", _set(dtype=7), (-3, -3, -3)),
+    ("group of 3", _set(num_heads=12, num_heads_kv=4), (-2, -2, -2)),
+    ("heads not a multiple of kv heads", _set(num_heads=6, num_heads_kv=4), (-2, -2, -2)),
+    ("negative num_heads_kv", _set(num_heads_kv=-2), (-2, -2, -2)),
+    ("stride too small", _set(stride=8), (-2, -2, -2)),
+    ("stride not a multiple of 8", _set(stride=4 * _ROW + 4), (-2, -2, -2)),
+    ("token stride too small", _set(token_stride=100), (WS, -2, -2)),
+    ("token stride not a multiple of 8", _set(token_stride=_ROW + 4), (WS, -2, -2)),
+    ("num_splits 1025", _set(num_splits=1025), (-2, -2, -2)),
+    ("kv_layout 3", _set(kv_layout=3), (-2, -2, -2)),
+    ("paged without a table", _paged(block_table=None), (-1, -1, -1)),
+    ("page_size 8", _paged(page_size=8, block_table_stride=8), (-2, -2, -2)),
+    ("page_size 24", _paged(page_size=24), (-2, -2, -2)),
+    ("table does not cover memory_max_len", _paged(block_table_stride=3), (-2, -2, -2)),
+    ("num_pages 0", _paged(num_pages=0), (-2, -2, -2)),
+    ("misaligned block_table", _paged(block_table=0x3002), (-2, -2, -2)),
+    ("well-formed paged call", _paged(), (WS, WS, WS)),
+    ("misaligned qkv", _set(qkv=0x1008), (-2, -2, -2)),
+    ("misaligned k_bias", _set(k_bias=0x1004), (-2, -2, -2)),
+    ("misaligned cu_tokens", _set(cu_tokens=0x4002), (WS, WS, -2)),
+    ("head-major cache", _set(kv_layout=_lib.KV_LAYOUTS["blhmd"]), (WS, WS, WS)),
+    ("workspace one byte short", _workspace(short=1), (-5, -5, -5)),
+    ("workspace of 16 bytes", _set(workspace=0x2000, workspace_bytes=16, num_splits=3), (-5, -5, -5)),
+    ("misaligned workspace", _workspace(address=0x2010), (-2, -2, -2)),
+    ("misaligned workspace, one byte short", _workspace(short=1, address=0x2010), (-5, -5, -5)),
+    ("bad idx_layer before head_dim 96", _set(idx_layer=1, head_dim=96), (-2, -2, -2)),
+    ("head_dim 96 before dtype 7", _set(head_dim=96, dtype=7), (-4, -4, -4)),
+    ("dtype 7 before a group of 3", _set(dtype=7, num_heads=12), (-3, -3, -3)),
+    ("num_splits 1025 before paged without a table", _paged(block_table=None, num_splits=1025), (-2, -2, -2)),
+    ("paged without a table before misaligned qkv", _paged(block_table=None, qkv=0x1008), (-1, -1, -1)),
+    ("qkv missing before a negative count", _set(qkv=None, count=-1), (-1, -1, -1)),
+]
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason="calls the decode entry points with fake device pointers")
+@pytest.mark.parametrize("entry", ENTRY_POINTS)
+def test_malformed_arguments_same_status_on_every_decode_entry_point(lib, entry):
+    for what, mutate, expected in MALFORMED:
+        st, err = _malformed_status(lib, entry, mutate)
+        want = expected[ENTRY_POINTS.index(entry)]
+        assert st == (-1 if want is WS else want), (what, entry, st, err)
+        assert err.startswith(entry.encode() + b":"), (what, entry, err)
+        assert (WS.encode() in err) == (want is WS), (what, entry, err)
+
+
 def test_product_never_imports_oracle():
     """Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may touch oracle/."""
     offenders = []

@@ -312,6 +312,29 @@ def test_chunk_rejection(sfa):
     np.testing.assert_allclose(o[0], want[0][0], atol=TOL[dtype], rtol=TOL[dtype])
 
 
+def test_chunk_exact_workspace_through_the_c_abi(sfa):
+    """sfa_decode_chunk itself, with a workspace of exactly sfa_decode_chunk_workspace_bytes(..., 3) bytes and a canary
+    behind it: bit-identical to the operator (which uses its roomy cached workspace) and nothing written past the end."""
+    from exact_workspace import call_with_exact_workspace, decode_problem
+    from starflashattention_amd import _lib, ops
+    B, n, H, Hkv, D, L, M, S = 2, 3, 4, 2, 64, 1, 128, 3
+    qkv, kc0, vc0, o0 = decode_problem((B, n), B, H, Hkv, D, L, M, 72, DEV)
+    sl = torch.tensor([0, 100], dtype=torch.int32, device=DEV)
+    z = torch.zeros(0, dtype=torch.float16, device=DEV)
+    kc1, vc1, o1 = kc0.clone(), vc0.clone(), o0.clone()
+    sfa.flash_decode_chunk(qkv, z, z, z, kc1, vc1, sl, o1, B, M, H, D, D, M, L, 0, num_splits=S, num_heads_kv=Hkv)
+    sfa.check_decode_status(DEV)
+    kc2, vc2, o2 = kc0.clone(), vc0.clone(), o0.clone()
+    a, *_ = ops._decode_args(qkv, z, z, z, kc2, vc2, sl, o2, B, M, H, D, D, M, L, 0, None, None, None, "blmhd", None, Hkv,
+                             tokens=n)
+    lib = _lib.load()
+    a.stride = 0
+    call_with_exact_workspace(a, lib.sfa_decode_chunk_workspace_bytes(B, H, Hkv, D, M, n, S), S,
+                              lambda args, stream: lib.sfa_decode_chunk(args, n, 0, stream), DEV)
+    assert torch.equal(o2, o1) and torch.equal(kc2, kc1) and torch.equal(vc2, vc1)
+    assert bool(torch.isfinite(o2.float()).all()) and not torch.equal(o2, o0) and not torch.equal(kc2, kc0)
+
+
 def test_chunk_at_scale_against_prefill(sfa):
     """B=4, H=32, D=128, bf16, blhmd, pos=2048, n=2048 against flash_attn_fwd(q_rot, K[:pos+n], V[:pos+n], causal)
     -- its bottom-right alignment is exactly j <= pos + t -- and 64 sampled rows against fp64."""

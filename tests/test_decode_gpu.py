@@ -526,6 +526,28 @@ def test_decode_gqa_workspace_sized_by_query_heads(sfa):
     np.testing.assert_allclose(o_old.float().cpu().numpy(), o_new.float().cpu().numpy(), atol=tol, rtol=tol)
 
 
+def test_decode_exact_workspace_through_the_c_abi(sfa):
+    """sfa_decode itself, with a workspace of exactly sfa_decode_workspace_bytes(..., 3) bytes and a canary behind it:
+    bit-identical to the operator (which uses its roomy cached workspace) and nothing written past the end."""
+    from exact_workspace import call_with_exact_workspace, decode_problem
+    from starflashattention_amd import _lib, ops
+    dev = torch.device("cuda:0")
+    B, H, Hkv, D, L, M, S = 3, 4, 2, 64, 1, 128, 3
+    qkv, kc0, vc0, o0 = decode_problem((B,), B, H, Hkv, D, L, M, 71, dev)
+    sl = torch.tensor([0, 70, 127], dtype=torch.int32, device=dev)
+    z = torch.zeros(0, dtype=torch.float16, device=dev)
+    kc1, vc1, o1 = kc0.clone(), vc0.clone(), o0.clone()
+    sfa.flash_decode(qkv, z, z, z, kc1, vc1, sl, o1, B, M, H, D, D, M, L, 0, num_splits=S, num_heads_kv=Hkv)
+    sfa.check_decode_status(dev)
+    kc2, vc2, o2 = kc0.clone(), vc0.clone(), o0.clone()
+    a, *_ = ops._decode_args(qkv, z, z, z, kc2, vc2, sl, o2, B, M, H, D, D, M, L, 0, None, None, None, "blmhd", None, Hkv)
+    lib = _lib.load()
+    a.stride = (H + 2 * Hkv) * D
+    call_with_exact_workspace(a, lib.sfa_decode_workspace_bytes(B, H, D, M, S), S, lib.sfa_decode, dev)
+    assert torch.equal(o2, o1) and torch.equal(kc2, kc1) and torch.equal(vc2, vc1)
+    assert bool(torch.isfinite(o2.float()).all()) and not torch.equal(o2, o0) and not torch.equal(kc2, kc0)
+
+
 def test_decode_layouts_agree_at_scale(sfa):
     """BASELINE config 4's sequence length and head count at a batch the box can hold thrice: the
     reference layout, the head-major layout and a randomly paged pool (non-temporal loads kick in:

@@ -398,6 +398,33 @@ def test_varlen_token_stride_through_the_c_abi(sfa):
     check(p, (o.float().cpu().numpy(), kc_d.float().cpu().numpy(), vc_d.float().cpu().numpy()), p.oracle())
 
 
+def test_varlen_exact_workspace_through_the_c_abi(sfa):
+    """sfa_decode_varlen itself, with a workspace of exactly sfa_decode_varlen_workspace_bytes(..., 3) bytes (status,
+    a plan of 3 entries, rotated Q, partials) and a canary behind it: bit-identical to the operator (which uses its
+    roomy cached workspace) and nothing written past the end."""
+    from exact_workspace import call_with_exact_workspace, decode_problem
+    from starflashattention_amd import _lib, ops
+    H, Hkv, D, L, M, S = 4, 2, 64, 1, 128, 3
+    ns, B, T = [0, 5, 1], 3, 8                             # two padding rows behind the six tokens
+    assert T * (H // Hkv) // 256 + B == 3
+    qkv, kc0, vc0, o0 = decode_problem((T,), B, H, Hkv, D, L, M, 73, DEV)
+    sl, cu = i32([9, 100, 127]), i32([0] + list(np.cumsum(ns)))
+    z = torch.zeros(0, dtype=torch.float16, device=DEV)
+    kc1, vc1, o1 = kc0.clone(), vc0.clone(), o0.clone()
+    sfa.flash_decode_varlen(qkv, z, z, z, kc1, vc1, sl, o1, cu, B, M, H, D, D, M, L, 0, num_splits=S, num_heads_kv=Hkv)
+    sfa.check_decode_status(DEV)
+    kc2, vc2, o2 = kc0.clone(), vc0.clone(), o0.clone()
+    a, *_ = ops._decode_args(qkv, z, z, z, kc2, vc2, sl, o2, B, M, H, D, D, M, L, 0, None, None, None, "blmhd", None, Hkv,
+                             packed=T)
+    lib = _lib.load()
+    a.stride = 0
+    call_with_exact_workspace(a, lib.sfa_decode_varlen_workspace_bytes(B, H, Hkv, D, M, T, S), S,
+                              lambda args, stream: lib.sfa_decode_varlen(args, ctypes.c_void_p(cu.data_ptr()), T, 0, stream),
+                              DEV)
+    assert torch.equal(o2, o1) and torch.equal(kc2, kc1) and torch.equal(vc2, vc1)
+    assert bool(torch.isfinite(o2[:6].float()).all()) and bool((o2[6:] == 7.0).all()) and not torch.equal(kc2, kc0)
+
+
 def test_varlen_at_scale(sfa):
     """B=64, H=32, D=128, bf16, blhmd, M=4096: one sequence with n=2048 at pos=2048, 63 with n=1 at pos=4095.  The long
     sequence against flash_attn_fwd(q_rot, K[:pos+n], V[:pos+n], causal) -- its bottom-right alignment is exactly
