@@ -20,6 +20,8 @@
  *   sfa_fill_16bit              <- init_half_array           src/flash_attn.h:11,   cu:493-510
  *   sfa_prefill_fwd             <- (no reference function; BASELINE.json configs 2,3,5)
  *   sfa_decode_chunk            <- (no reference function: prompt ingestion before the first decode step)
+ *   sfa_decode_kv8              <- (no reference function: sfa_decode over an fp8 (e4m3) KV cache)
+ *   sfa_kv8_quantize            <- (no reference function: 16-bit cache rows -> fp8 cache rows)
  * The Python-facing mha_fwd_cuda (src/flash_api.cpp:42-68) and the C++ template
  * surface (src/flash_attn.h) in this repo are thin layers over these symbols.
  */
@@ -39,7 +41,9 @@ extern "C" {
  *      a block_table entry outside the pool on the APPEND page now rejects the sequence; sfa_debug_set
  *   4  sfa_debug_get, sfa_decode_workspace_bytes_gqa added (nothing changed); sfa_decode_chunk and
  *      sfa_decode_chunk_workspace_bytes added later under the same version, with no layout or meaning change:
- *      callers detect them by symbol */
+ *      callers detect them by symbol
+ *      sfa_decode_kv8 and sfa_kv8_quantize (fp8 KV cache) added under the same version, beside an unchanged
+ *      sfa_decode_args: callers detect these entry points by symbol */
 #define SFA_ABI_VERSION 4
 
 typedef enum sfa_status {
@@ -230,6 +234,45 @@ int    sfa_decode_varlen(const sfa_decode_args *args, const void *cu_tokens, int
                          int64_t qkv_token_stride, void *stream);
 size_t sfa_decode_varlen_workspace_bytes(int batch_size, int num_heads, int num_heads_kv, int head_dim,
                                          int memory_max_len, int total_tokens, int num_splits);
+
+/* ---- decode over an fp8 KV cache ---------------------------------------------------- */
+/*
+ * sfa_decode with caches of one byte per element.  Every field of args keeps its sfa_decode meaning, except:
+ *   k_cache_table / v_cache_table   OCP e4m3 bytes (1-4-3, bias 7, max 448, no infinities, 0x7F / 0xFF = NaN: torch's
+ *                  float8_e4m3fn), in the same three layouts; the row, head and page strides keep their values in
+ *                  elements, which now are bytes.  16-byte aligned.
+ *   dtype          still the dtype of qkv, the biases, the rotary tables and o: fp16 or bf16
+ *   head_dim       64 or 128 (256 returns SFA_ERR_UNSUPPORTED_HEAD_DIM)
+ *   k_scale, v_scale   device fp32 [num_heads_kv], 4-byte aligned, one scale per kv head; NULL = 1.0.  The scales must
+ *                  be finite and > 0: they are device data, so this is the caller's contract and is not checked.
+ * num_heads / num_heads_kv in {1, 2, 4, 8, 16}; paging, bias, partial rotary, the rotary tables and num_splits as in
+ * sfa_decode.
+ * Semantics, for every (b, h), hk = the kv head of h:
+ *   k16, v16 = exactly what sfa_decode would have stored (bias, RoPE in fp32, rounded to the 16-bit dtype)
+ *   k8 = q8(k16 / k_scale[hk]),  v8 = q8(v16 / v_scale[hk])     written at row pos; no other byte of a cache changes
+ *   q8(x) = e4m3_rne(clamp(x, -448, 448)): IEEE fp32 division, saturating, ties to even, NaN stays NaN (0x7F)
+ *   o = softmax(q16 . (k_scale[hk] * K8[0..pos])^T * head_dim_inv) . (v_scale[hk] * V8[0..pos])     (fp32 accumulate)
+ * The new token takes part through its QUANTISED value: the output of a step is a function of the cache contents
+ * after the step.
+ * Rejection (pos out of range, a bad append page, a bad read page) behaves exactly as in sfa_decode: the same status
+ * bits, NaN in o[b], nothing stored, a bad read page never dereferenced.
+ * Workspace: the size and layout of sfa_decode_workspace_bytes_gqa; the same workspace and status word serve sfa_decode
+ * and sfa_decode_kv8 calls (and the chunk / varlen calls) on the same stream.
+ */
+int sfa_decode_kv8(const sfa_decode_args *args, const float *k_scale, const float *v_scale, void *stream);
+
+/*
+ * How a prompt gets into an fp8 cache: it runs through sfa_decode_chunk / sfa_decode_varlen on a 16-bit staging cache
+ * (one layer of it is enough), then its rows are quantised into the fp8 cache:
+ *   dst[r*dst_row_stride + h*dst_head_stride + d] = q8(src[r*src_row_stride + h*src_head_stride + d] / scale[h])
+ * for r < rows, h < num_heads_kv, d < head_dim (64 or 128); rows = 0 does nothing.  src holds `dtype` (fp16 / bf16)
+ * elements, dst bytes.  Strides are in elements and multiples of 16, dst and src 16-byte aligned; scale is device fp32
+ * [num_heads_kv] (finite, > 0, not checked) or NULL = 1.0.  One call covers a (sequence, layer) slice of either
+ * contiguous layout, or one page.
+ */
+int sfa_kv8_quantize(void *dst, const void *src, const float *scale, int64_t rows, int num_heads_kv, int head_dim,
+                     int64_t src_row_stride, int64_t src_head_stride,
+                     int64_t dst_row_stride, int64_t dst_head_stride, int dtype, void *stream);
 
 /* ---- prefill: O = softmax(mask(Q K^T * scale)) V ------------------------------- */
 /*

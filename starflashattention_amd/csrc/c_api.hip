@@ -139,6 +139,8 @@ struct EntryPoint {
 constexpr EntryPoint kDecode = {"sfa_decode", "num_tokens", true, false, false};
 constexpr EntryPoint kChunk = {"sfa_decode_chunk", "num_tokens", false, true, false};
 constexpr EntryPoint kVarlen = {"sfa_decode_varlen", "total_tokens", false, true, true};
+// (head_dim 256 passes the shared checks and is refused by sfa_decode_kv8 itself, with a message of its own)
+constexpr EntryPoint kKv8 = {"sfa_decode_kv8", "num_tokens", true, false, false};
 
 // What the entry points check alike, before any HIP call, and what they derive on the way.  sfa_decode is the case of
 // one token per sequence (count = 1) with no token stride.
@@ -354,6 +356,59 @@ int sfa_decode(const sfa_decode_args *a, void *stream) {
     p.part_o = (float *)(ws + w.part_o);
     p.part_ml = (float2 *)(ws + w.part_ml);
     return launch_decode(p, a->dtype, a->head_dim, (hipStream_t)stream);
+}
+
+// sfa_decode with e4m3 caches: the workspace, the split count and the status word are sfa_decode's
+int sfa_decode_kv8(const sfa_decode_args *a, const float *k_scale, const float *v_scale, void *stream) {
+    DecodeCall dc;
+    if (const int rc = validate_decode_call(kKv8, a, 1, 0, &dc)) return rc;
+    if (a->head_dim == 256)
+        return fail(SFA_ERR_UNSUPPORTED_HEAD_DIM,
+                    "sfa_decode_kv8: head_dim 256 is not supported over an fp8 cache yet (64 or 128; sfa_decode serves "
+                    "256 on a 16-bit cache)");
+    if (((uintptr_t)k_scale | (uintptr_t)v_scale) & 3)
+        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_kv8: k_scale / v_scale must be 4-byte aligned");
+    if (a->batch_size == 0) return SFA_OK;
+
+    const size_t bh = (size_t)a->batch_size * a->num_heads;
+    // one workgroup per kv head: the split count follows the kv-head count, as in grouped sfa_decode, and a workspace
+    // sized by the query-head count gets the largest split count it holds
+    int S = a->num_splits > 0 ? a->num_splits : auto_splits(a->batch_size, dc.hkv, a->memory_max_len);
+    if (a->num_splits <= 0 && a->workspace)
+        while (S > 1 && a->workspace_bytes < decode_workspace(0, 0, bh, S, a->head_dim).total) --S;
+    const DecodeWorkspace w = decode_workspace(0, 0, bh, S, a->head_dim);
+    if (const int rc = check_workspace(kKv8, a, w.total)) return rc;
+
+    Kv8KernelParams p;
+    memset(&p, 0, sizeof(p));
+    p.d = decode_params(a, dc.hkv, dc.page_shift, S, dc.stride);
+    char *ws = (char *)a->workspace;
+    p.d.part_o = (float *)(ws + w.part_o);
+    p.d.part_ml = (float2 *)(ws + w.part_ml);
+    p.k_scale = k_scale;
+    p.v_scale = v_scale;
+    return launch_decode_kv8(p, a->dtype, a->head_dim, (hipStream_t)stream);
+}
+
+int sfa_kv8_quantize(void *dst, const void *src, const float *scale, int64_t rows, int num_heads_kv, int head_dim,
+                     int64_t src_row_stride, int64_t src_head_stride, int64_t dst_row_stride, int64_t dst_head_stride,
+                     int dtype, void *stream) {
+    if (!dst || !src) return fail(SFA_ERR_NULL_POINTER, "sfa_kv8_quantize: dst/src must be non-NULL");
+    if (rows < 0 || num_heads_kv <= 0)
+        return fail(SFA_ERR_BAD_SHAPE, "sfa_kv8_quantize: rows=%lld num_heads_kv=%d", (long long)rows, num_heads_kv);
+    if (head_dim != 64 && head_dim != 128)
+        return fail(SFA_ERR_UNSUPPORTED_HEAD_DIM, "sfa_kv8_quantize: head_dim %d not in {64, 128}", head_dim);
+    if (dtype != SFA_DTYPE_FP16 && dtype != SFA_DTYPE_BF16)
+        return fail(SFA_ERR_BAD_DTYPE, "sfa_kv8_quantize: dtype %d is not fp16(0)/bf16(1)", dtype);
+    const int64_t st[4] = {src_row_stride, src_head_stride, dst_row_stride, dst_head_stride};
+    for (int i = 0; i < 4; ++i)
+        if (st[i] < 0 || (st[i] % 16) != 0)
+            return fail(SFA_ERR_BAD_SHAPE, "sfa_kv8_quantize: strides must be >= 0 and multiples of 16 elements");
+    if (((uintptr_t)dst | (uintptr_t)src) & 15)
+        return fail(SFA_ERR_BAD_SHAPE, "sfa_kv8_quantize: dst and src must be 16-byte aligned");
+    if ((uintptr_t)scale & 3) return fail(SFA_ERR_BAD_SHAPE, "sfa_kv8_quantize: scale must be 4-byte aligned");
+    return launch_kv8_quantize(dst, src, scale, rows, num_heads_kv, head_dim, src_row_stride, src_head_stride,
+                               dst_row_stride, dst_head_stride, dtype, (hipStream_t)stream);
 }
 
 // (query rows per (batch, kv head) = num_tokens * group; bhr of them in all)

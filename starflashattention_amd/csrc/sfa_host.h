@@ -72,6 +72,13 @@ struct VarlenKernelParams {
     int bound;              // plan entries = grid.x of the attention kernel
 };
 
+// sfa_decode_kv8 (decode_kv8_kernel.hip): caches of one byte per element (e4m3) with a scale per kv head.
+struct Kv8KernelParams {
+    DecodeKernelParams d;   // every field keeps its sfa_decode meaning; d.k_cache / d.v_cache point to bytes, the cache
+                            // strides are in elements = bytes
+    const float *k_scale, *v_scale;     // [Hkv] each, nullptr = 1.0
+};
+
 struct PrefillKernelParams {
     const uint16_t *q, *k, *v;
     uint16_t *o;
@@ -94,6 +101,11 @@ int launch_decode_gqa_mfma(const DecodeKernelParams &p, int dtype, int head_dim,
 int launch_decode_combine(const DecodeKernelParams &p, int dtype, int head_dim, hipStream_t stream);
 int launch_decode_chunk(const ChunkKernelParams &p, int dtype, int head_dim, hipStream_t stream);
 int launch_decode_varlen(const VarlenKernelParams &p, int dtype, int head_dim, hipStream_t stream);
+// decode_kv8_kernel.hip: the attention kernel over e4m3 caches plus the split combine; the 16-bit -> e4m3 row copy
+int launch_decode_kv8(const Kv8KernelParams &p, int dtype, int head_dim, hipStream_t stream);
+int launch_kv8_quantize(void *dst, const void *src, const float *scale, long long rows, int Hkv, int head_dim,
+                        long long src_row, long long src_head, long long dst_row, long long dst_head, int dtype,
+                        hipStream_t stream);
 int launch_prefill(const PrefillKernelParams &p, int dtype, int head_dim, bool causal, hipStream_t stream);
 int launch_prefill_no_keys(const PrefillKernelParams &p, int head_dim, hipStream_t stream);
 int launch_rotary_table(void *cos_t, void *sin_t, int max_seq_len, int rot_dim, int dtype, hipStream_t stream);

@@ -11,6 +11,8 @@ libStarFlashAttention.so.  The public operators:
                       speculative verification (new entry point).
   flash_decode_varlen(...) the same with a token count of its own per sequence, packed: one call for a mixed
                       prefill / verify / decode step (new entry point).
+  flash_decode_kv8(...)  flash_decode over an fp8 (e4m3) KV cache with a scale per kv head; quantize_kv8(...) moves
+                      16-bit cache rows into such a cache (new entry points).
 """
 import ctypes
 import math
@@ -20,6 +22,8 @@ import torch
 from . import _lib
 
 _DTYPES = {torch.float16: _lib.DTYPE_FP16, torch.bfloat16: _lib.DTYPE_BF16}
+
+_KV8_DTYPES = (torch.uint8, torch.float8_e4m3fn)     # an e4m3 cache, as bytes or as torch's own type
 
 _workspaces = {}          # (device index, stream) -> torch.uint8 tensor
 _sync_checks = False
@@ -75,11 +79,13 @@ def release_workspaces():
 
 def _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size, memory_max_len,
                  num_heads, head_dim, rotary_embedding_dim, max_input_length, num_layer, idx_layer, rotary_cos_table,
-                 rotary_sin_table, softmax_scale, kv_layout, block_table, num_heads_kv, tokens=None, packed=None):
+                 rotary_sin_table, softmax_scale, kv_layout, block_table, num_heads_kv, tokens=None, packed=None,
+                 kv8=False):
     """Check the tensors of one decode call and fill its sfa_decode_args, all but the workspace, num_splits and stride.
     tokens None: flash_decode (qkv [B, 3, H, D] or [B, H + 2*Hkv, D], o [B, H, D]); tokens = n: flash_decode_chunk
     (qkv [B, n, 3, H, D] or [B, n, H + 2*Hkv, D], o [B, n, H, D]); packed = T: flash_decode_varlen (qkv [T, 3, H, D] or
-    [T, H + 2*Hkv, D], o [T, H, D]: the tokens of all sequences, one after another).  Returns (args, B, H, Hkv, D, M)."""
+    [T, H + 2*Hkv, D], o [T, H, D]: the tokens of all sequences, one after another).  kv8: the caches hold e4m3 bytes
+    (torch.uint8 or torch.float8_e4m3fn).  Returns (args, B, H, Hkv, D, M)."""
     _require(isinstance(qkv, torch.Tensor) and qkv.dtype in _DTYPES,
              f"qkv must be a float16 or bfloat16 tensor (got {getattr(qkv, 'dtype', type(qkv))})")
     dt, dev = qkv.dtype, qkv.device
@@ -102,8 +108,11 @@ def _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_
     else:
         _require(block_table is None, "block_table is only meaningful with kv_layout='paged'")
         cache_shape = (B, L, M, Hkv, D) if kv_layout == "blmhd" else (B, L, Hkv, M, D)
-    _check_gpu_tensor(k_cache_table, "k_cache_table", dt, cache_shape, dev)
-    _check_gpu_tensor(v_cache_table, "v_cache_table", dt, cache_shape, dev)
+    for name, t in (("k_cache_table", k_cache_table), ("v_cache_table", v_cache_table)):
+        if kv8:
+            _require(isinstance(t, torch.Tensor) and t.dtype in _KV8_DTYPES,
+                     f"{name} must be a uint8 or float8_e4m3fn tensor (got {getattr(t, 'dtype', type(t))})")
+        _check_gpu_tensor(t, name, t.dtype if kv8 else dt, cache_shape, dev)
     biases = []
     for name, t in (("q_bias", q_bias), ("k_bias", k_bias), ("v_bias", v_bias)):
         if t is None or t.numel() == 0:
@@ -179,6 +188,62 @@ def flash_decode(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_
             _lib.check(lib.sfa_decode_reset_status(ctypes.c_void_p(ws.data_ptr()), _stream_ptr(dev)))
         _call_decode(dev, a, (H + 2 * Hkv) * D, S, ws, lib.sfa_decode)
     return o
+
+
+def _kv8_scale(t, name, Hkv, dev):
+    if t is None:
+        return None
+    _check_gpu_tensor(t, name, torch.float32, (Hkv,), dev)
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def flash_decode_kv8(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o,
+                     batch_size, memory_max_len, num_heads, head_dim, rotary_embedding_dim,
+                     max_input_length, num_layer, idx_layer, *, num_splits=0,
+                     rotary_cos_table=None, rotary_sin_table=None, softmax_scale=None, kv_layout="blmhd",
+                     block_table=None, num_heads_kv=None, k_scale=None, v_scale=None):
+    """flash_decode over an fp8 KV cache (include/star_flash_attn.h, sfa_decode_kv8).  The caches are torch.uint8 or
+    torch.float8_e4m3fn tensors in flash_decode's layouts; qkv, the biases, the rotary tables and o stay fp16 / bf16;
+    head_dim 64 or 128.  k_scale / v_scale: float32 device tensors [num_heads_kv], one scale per kv head, None = 1.0.
+    The new token is stored as q8(x / scale) and attends through that stored value.  Returns `o`."""
+    lib = _lib.load()
+    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
+                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
+                                      kv_layout, block_table, num_heads_kv, kv8=True)
+    dev = qkv.device
+    ks, vs = _kv8_scale(k_scale, "k_scale", Hkv, dev), _kv8_scale(v_scale, "v_scale", Hkv, dev)
+    with torch.cuda.device(dev):
+        S = int(num_splits) if num_splits and num_splits > 0 else lib.sfa_decode_auto_splits(B, Hkv, D, M)
+        ws = _workspace(dev, lib.sfa_decode_workspace_bytes(B, H, D, M, S))
+        _call_decode(dev, a, (H + 2 * Hkv) * D, S, ws, lambda args, stream: lib.sfa_decode_kv8(args, ks, vs, stream))
+    return o
+
+
+def quantize_kv8(src, scale=None, out=None):
+    """16-bit cache rows -> e4m3 bytes (include/star_flash_attn.h, sfa_kv8_quantize): out[r, h, d] = q8(src[r, h, d] /
+    scale[h]).  src is a [rows, Hkv, D] fp16 / bf16 view with any row and head strides that are multiples of 16
+    elements and a contiguous last axis (a (sequence, layer) slice of either contiguous cache layout, or a page); out
+    is such a view of a torch.uint8 / torch.float8_e4m3fn cache (None: a new contiguous uint8 tensor); scale a float32
+    [Hkv] device tensor or None = 1.0.  Returns `out`."""
+    lib = _lib.load()
+    _require(isinstance(src, torch.Tensor) and src.is_cuda and src.dtype in _DTYPES and src.dim() == 3,
+             "src must be a [rows, Hkv, D] float16 or bfloat16 tensor on a HIP device")
+    rows, Hkv, D = (int(x) for x in src.shape)
+    dev = src.device
+    if out is None:
+        out = torch.empty((rows, Hkv, D), dtype=torch.uint8, device=dev)
+    _require(isinstance(out, torch.Tensor) and out.dtype in _KV8_DTYPES and out.device == dev and
+             tuple(out.shape) == (rows, Hkv, D), f"out must be a uint8 or float8_e4m3fn tensor of shape {(rows, Hkv, D)} on {dev}")
+    _require(src.stride(2) == 1 and out.stride(2) == 1, "the last axis of src and out must be contiguous")
+    sc = _kv8_scale(scale, "scale", Hkv, dev)
+    if rows == 0:
+        return out
+    with torch.cuda.device(dev):
+        _lib.check(lib.sfa_kv8_quantize(ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(src.data_ptr()), sc, rows, Hkv, D,
+                                        src.stride(0), src.stride(1), out.stride(0), out.stride(1), _DTYPES[src.dtype],
+                                        _stream_ptr(dev)))
+    return out
 
 
 def flash_decode_chunk(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o,
