@@ -104,6 +104,8 @@ const char *sfa_last_error(void);            /* thread-local, never NULL        
  * Caches are [batch, num_layer, memory_max_len, num_heads, head_dim], contiguous
  * (kv_layout = SFA_KV_BLMHD), or head-major with kv_layout = SFA_KV_BLHMD.
  * seq_len is NOT incremented (caller's job, as in the reference).
+ * Cache rows beyond pos (beyond pos + n - 1 for the calls that append n tokens), the other layers, and
+ * block_table entries past the last page a sequence needs are never read and may hold anything.
  * A sequence whose seq_len is out of range -- or, with paged caches, whose
  * block_table entry for the page the new token goes to lies outside [0, num_pages) --
  * is left untouched in the caches, gets NaN in o[b] and raises the sticky status word
