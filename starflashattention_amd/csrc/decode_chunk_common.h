@@ -1,35 +1,15 @@
-// Device helpers of the multi-token decode step (decode_chunk_body.h): the per-element bias / RoPE
-// arithmetic of the single-token decode kernels, restated once so that a chunk of n tokens writes the cache
-// bytes n successive sfa_decode calls would, and the chunk's rejection rule.
+// Device helpers of the multi-token decode step (decode_chunk_body.h): the rotation of the single-token decode kernels
+// applied to one vector, so that a chunk of n tokens writes the cache bytes n successive sfa_decode calls would, and the
+// chunk's rejection rule.  The bias, cos / sin and head offset helpers it shares with those kernels are decode_common.h's.
 #pragma once
 #include "decode_common.h"
 
 namespace sfa {
 namespace chunk {
 
-// x[0..8) += bias[0..8) (fp32), as decode_kernel.hip adds q / k / v bias
-template <class Tr>
-__device__ __forceinline__ void add_bias8(float (&x)[8], const uint16_t *bias) {
-    float t[8];
-    decode::unpack8<Tr>(*reinterpret_cast<const uint4 *>(bias), t);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) x[j] += t[j];
-}
-
-// cos / sin of RoPE pair pj at position pos: decode_kernel.hip's recipe -- the LUT row pos, or fp32 powf / sincosf.
-template <class Tr>
-__device__ __forceinline__ void rope_cs(int pj, int pos, const DecodeKernelParams &p, float &c, float &s) {
-    const int rot = p.rot_dim;
-    if (p.cos_tab) {
-        const long long ti = (long long)pos * (rot >> 1) + pj;
-        c = Tr::to_f32(p.cos_tab[ti]);
-        s = Tr::to_f32(p.sin_tab[ti]);
-    } else {
-        const float inv_freq = 1.0f / powf(10000.0f, (float)(2 * pj) / (float)rot);
-        const float ang = (float)pos * inv_freq;
-        sincosf(ang, &s, &c);
-    }
-}
+using decode::add_bias8;
+using decode::rope_cs;
+using decode::head_base;
 
 // Interleaved RoPE of this lane's 8 dims (pairs sub*4 .. sub*4+3), cos / sin of pair pj in cs[pj] / sn[pj]:
 // decode_kernel.hip's rotation, applied to one vector.
@@ -61,15 +41,6 @@ __device__ __forceinline__ int reject_code(const DecodeKernelParams &p, int n, i
         if (__syncthreads_or(bad)) return 2;
     }
     return 0;
-}
-
-// Element offset of row 0 of kv head hk in the (b, layer) cache (contiguous layouts: row r is r * kv_row_stride
-// further), or of the (layer, hk) slice of page 0 of the pool (paged: row r is page * page_stride +
-// (r & page_mask) * kv_row_stride further).  As in decode_kernel.hip.
-template <int D, bool PAGED>
-__device__ __forceinline__ long long head_base(const DecodeKernelParams &p, int b, int hk) {
-    if (PAGED) return (long long)p.layer * (p.kv_row_stride << p.page_shift) + (long long)hk * p.kv_head_stride;
-    return ((long long)b * p.L + p.layer) * p.M * p.Hkv * D + (long long)hk * p.kv_head_stride;
 }
 
 }  // namespace chunk

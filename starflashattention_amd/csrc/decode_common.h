@@ -1,4 +1,5 @@
-// Device helpers shared by the decode kernels (decode_kernel.hip, decode_gqa_kernel.hip).
+// Device helpers shared by the decode kernels: decode_kernel.hip, decode_gqa_kernel.hip, the two matrix-core kernels
+// (through decode_mfma_common.h) and the multi-token step (through decode_chunk_common.h).
 #pragma once
 #include "sfa_device.h"
 #include "sfa_host.h"
@@ -31,6 +32,39 @@ template <class Tr>
 __device__ __forceinline__ uint4 pack8(const float (&x)[8]) {
     return make_uint4(Tr::pack2(x[0], x[1]), Tr::pack2(x[2], x[3]),
                       Tr::pack2(x[4], x[5]), Tr::pack2(x[6], x[7]));
+}
+
+// x[0..8) += bias[0..8) (fp32), as decode_kernel.hip adds q / k / v bias
+template <class Tr>
+__device__ __forceinline__ void add_bias8(float (&x)[8], const uint16_t *bias) {
+    float t[8];
+    unpack8<Tr>(*reinterpret_cast<const uint4 *>(bias), t);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) x[j] += t[j];
+}
+
+// cos / sin of RoPE pair pj at position pos: decode_kernel.hip's recipe -- the LUT row pos, or fp32 powf / sincosf.
+template <class Tr>
+__device__ __forceinline__ void rope_cs(int pj, int pos, const DecodeKernelParams &p, float &c, float &s) {
+    const int rot = p.rot_dim;
+    if (p.cos_tab) {
+        const long long ti = (long long)pos * (rot >> 1) + pj;
+        c = Tr::to_f32(p.cos_tab[ti]);
+        s = Tr::to_f32(p.sin_tab[ti]);
+    } else {
+        const float inv_freq = 1.0f / powf(10000.0f, (float)(2 * pj) / (float)rot);
+        const float ang = (float)pos * inv_freq;
+        sincosf(ang, &s, &c);
+    }
+}
+
+// Element offset of row 0 of kv head hk in the (b, layer) cache (contiguous layouts: row r is r * kv_row_stride
+// further), or of the (layer, hk) slice of page 0 of the pool (paged: row r is page * page_stride +
+// (r & page_mask) * kv_row_stride further).  As in decode_kernel.hip.
+template <int D, bool PAGED>
+__device__ __forceinline__ long long head_base(const DecodeKernelParams &p, int b, int hk) {
+    if (PAGED) return (long long)p.layer * (p.kv_row_stride << p.page_shift) + (long long)hk * p.kv_head_stride;
+    return ((long long)b * p.L + p.layer) * p.M * p.Hkv * D + (long long)hk * p.kv_head_stride;
 }
 
 // 16-byte cache-row load; NT = non-temporal (the cache rows are read exactly once per step)

@@ -16,9 +16,13 @@
 
 namespace sfa {
 
+bool decode_nt(const DecodeKernelParams &p, int head_dim, int elem_bytes) {
+    if (const int k = g_knobs.decode_nt.load(std::memory_order_relaxed); k >= 0) return k != 0;
+    return 2ll * elem_bytes * p.B * p.L * p.M * p.Hkv * head_dim > (256ll << 20);
+}
+
 int launch_decode(const DecodeKernelParams &p, int dtype, int head_dim, hipStream_t stream) {
-    bool nt = 4ll * p.B * p.L * p.M * p.Hkv * head_dim > (256ll << 20);
-    if (const int k = g_knobs.decode_nt.load(std::memory_order_relaxed); k >= 0) nt = k != 0;
+    const bool nt = decode_nt(p, head_dim, 2);
 
     const int group = p.H / p.Hkv;
     const int knob = g_knobs.decode_gqa_mfma.load(std::memory_order_relaxed);

@@ -93,6 +93,8 @@ struct PrefillKernelParams {
 };
 
 int launch_decode(const DecodeKernelParams &p, int dtype, int head_dim, hipStream_t stream);     // decode_dispatch.hip
+// non-temporal cache loads? (both caches of elem_bytes per element against the Infinity Cache, or the decode_nt knob)
+bool decode_nt(const DecodeKernelParams &p, int head_dim, int elem_bytes);                       // decode_dispatch.hip
 // the attention kernels launch_decode chooses from (validated dtype / head_dim; nt: non-temporal cache loads) and the
 // split combine
 int launch_decode_mha(const DecodeKernelParams &p, int dtype, int head_dim, bool nt, hipStream_t stream);
