@@ -22,6 +22,7 @@
  *   sfa_decode_chunk            <- (no reference function: prompt ingestion before the first decode step)
  *   sfa_decode_kv8              <- (no reference function: sfa_decode over an fp8 (e4m3) KV cache)
  *   sfa_kv8_quantize            <- (no reference function: 16-bit cache rows -> fp8 cache rows)
+ *   sfa_decode_window           <- (no reference function: sfa_decode over the last `window` positions)
  * The Python-facing mha_fwd_cuda (src/flash_api.cpp:42-68) and the C++ template
  * surface (src/flash_attn.h) in this repo are thin layers over these symbols.
  */
@@ -43,7 +44,9 @@ extern "C" {
  *      sfa_decode_chunk_workspace_bytes added later under the same version, with no layout or meaning change:
  *      callers detect them by symbol
  *      sfa_decode_kv8 and sfa_kv8_quantize (fp8 KV cache) added under the same version, beside an unchanged
- *      sfa_decode_args: callers detect these entry points by symbol */
+ *      sfa_decode_args: callers detect these entry points by symbol
+ *      sfa_decode_window and sfa_decode_window_workspace_bytes (sliding-window decode) added under the same version,
+ *      beside an unchanged sfa_decode_args: callers detect them by symbol */
 #define SFA_ABI_VERSION 4
 
 typedef enum sfa_status {
@@ -275,6 +278,35 @@ int sfa_decode_kv8(const sfa_decode_args *args, const float *k_scale, const floa
 int sfa_kv8_quantize(void *dst, const void *src, const float *scale, int64_t rows, int num_heads_kv, int head_dim,
                      int64_t src_row_stride, int64_t src_head_stride,
                      int64_t dst_row_stride, int64_t dst_head_stride, int dtype, void *stream);
+
+/* ---- decode with a sliding window --------------------------------------------------- */
+/*
+ * sfa_decode for a sliding-window attention layer.  Every field of args keeps its sfa_decode meaning: bias, RoPE at
+ * pos = seq_len[b], the rotary tables, partial rotary, the append at row pos, fp16 / bf16, head_dim 64 / 128 / 256, the
+ * three kv_layouts, num_heads / num_heads_kv in {1, 2, 4, 8, 16}, the rejection rules and the status word.  The only
+ * difference is the key range.  With lo = max(0, pos + 1 - window):
+ *   o[b, h, :] = softmax(q . K[lo..pos]^T * head_dim_inv) . V[lo..pos]
+ * The token sees itself and the window - 1 rows before it (flash-attn's window_size = (window - 1, 0)).
+ *   window >= 1     window < 1 returns SFA_ERR_BAD_SHAPE.  window = 1 attends to the new token only; window > pos for
+ *                   every sequence is plain sfa_decode.
+ * Cache rows are absolute positions (a ring-buffer cache is not supported).  What the window promises:
+ *   - cache rows below lo are never read and may hold anything (as do the rows beyond pos and the other layers);
+ *   - in a paged cache, a block_table entry whose page lies wholly below lo (entries [0, lo / page_size)) is never
+ *     read and may hold any value, -1 included: a server may free those pages;
+ *   - only a bad entry on a page that intersects [lo, pos] raises SFA_ERR_BLOCK_TABLE_RANGE (on the append page it
+ *     rejects the sequence, on a read page it makes the affected outputs NaN, as in sfa_decode);
+ *   - lo is computed on the device from seq_len: the call allocates nothing, never synchronises and may be captured
+ *     in a graph and replayed with other seq_len contents.
+ * Workspace: the layout of sfa_decode (the status block, then the fp32 partials).  With num_splits <= 0 the split
+ * count is sfa_decode_auto_splits(batch_size, num_heads_kv, head_dim, min(window, memory_max_len)) -- sfa_decode's rule
+ * over the rows a sequence can read, so a short window is not split -- and sfa_decode_window_workspace_bytes sizes for
+ * that count.  A workspace sized by sfa_decode_workspace_bytes_gqa is never too small; one that holds fewer splits than
+ * the library would pick gets the largest count it holds, as in sfa_decode.  The same workspace and status word serve
+ * every decode entry point on a stream.
+ */
+int    sfa_decode_window(const sfa_decode_args *args, int window, void *stream);
+size_t sfa_decode_window_workspace_bytes(int batch_size, int num_heads, int num_heads_kv, int head_dim,
+                                         int memory_max_len, int window, int num_splits);
 
 /* ---- prefill: O = softmax(mask(Q K^T * scale)) V ------------------------------- */
 /*

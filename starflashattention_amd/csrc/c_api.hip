@@ -128,7 +128,7 @@ static DecodeKernelParams decode_params(const sfa_decode_args *a, int hkv, int p
     return p;
 }
 
-// What sets the three decode entry points apart in the argument checks they share
+// What sets the decode entry points apart in the argument checks they share
 struct EntryPoint {
     const char *fn;             // names the entry point in the error text
     const char *count_name;     // its token count: num_tokens per sequence, or, packed, total_tokens over all sequences
@@ -141,6 +141,7 @@ constexpr EntryPoint kChunk = {"sfa_decode_chunk", "num_tokens", false, true, fa
 constexpr EntryPoint kVarlen = {"sfa_decode_varlen", "total_tokens", false, true, true};
 // (head_dim 256 passes the shared checks and is refused by sfa_decode_kv8 itself, with a message of its own)
 constexpr EntryPoint kKv8 = {"sfa_decode_kv8", "num_tokens", true, false, false};
+constexpr EntryPoint kWindow = {"sfa_decode_window", "num_tokens", true, false, false};
 
 // What the entry points check alike, before any HIP call, and what they derive on the way.  sfa_decode is the case of
 // one token per sequence (count = 1) with no token stride.
@@ -388,6 +389,44 @@ int sfa_decode_kv8(const sfa_decode_args *a, const float *k_scale, const float *
     p.k_scale = k_scale;
     p.v_scale = v_scale;
     return launch_decode_kv8(p, a->dtype, a->head_dim, (hipStream_t)stream);
+}
+
+// sfa_decode with a sliding window.  The split count is sfa_decode's rule over the rows a sequence can read,
+// min(window, memory_max_len), by kv-head count: a short window is not split into slivers.
+static int window_auto_splits(int B, int hkv, int M, int window) {
+    return auto_splits(B, hkv, window < M ? (window > 1 ? window : 1) : M);
+}
+
+size_t sfa_decode_window_workspace_bytes(int batch_size, int num_heads, int num_heads_kv, int head_dim,
+                                         int memory_max_len, int window, int num_splits) {
+    if (batch_size <= 0 || num_heads <= 0 || head_dim <= 0 || memory_max_len <= 0) return kStatusBytes;
+    const int hkv = num_heads_kv > 0 ? num_heads_kv : num_heads;
+    const int S = num_splits > 0 ? num_splits : window_auto_splits(batch_size, hkv, memory_max_len, window);
+    return sfa_decode_workspace_bytes(batch_size, num_heads, head_dim, memory_max_len, S);
+}
+
+int sfa_decode_window(const sfa_decode_args *a, int window, void *stream) {
+    DecodeCall dc;
+    if (const int rc = validate_decode_call(kWindow, a, 1, 0, &dc)) return rc;
+    if (window < 1) return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_window: window=%d must be >= 1", window);
+    if (a->batch_size == 0) return SFA_OK;
+
+    const size_t bh = (size_t)a->batch_size * a->num_heads;
+    // as in sfa_decode: a workspace sized for fewer splits than the library would pick gets the largest count it holds
+    int S = a->num_splits > 0 ? a->num_splits : window_auto_splits(a->batch_size, dc.hkv, a->memory_max_len, window);
+    if (a->num_splits <= 0 && a->workspace)
+        while (S > 1 && a->workspace_bytes < decode_workspace(0, 0, bh, S, a->head_dim).total) --S;
+    const DecodeWorkspace w = decode_workspace(0, 0, bh, S, a->head_dim);
+    if (const int rc = check_workspace(kWindow, a, w.total)) return rc;
+
+    WindowKernelParams p;
+    memset(&p, 0, sizeof(p));
+    p.d = decode_params(a, dc.hkv, dc.page_shift, S, dc.stride);
+    char *ws = (char *)a->workspace;
+    p.d.part_o = (float *)(ws + w.part_o);
+    p.d.part_ml = (float2 *)(ws + w.part_ml);
+    p.window = window;
+    return launch_decode_window(p, a->dtype, a->head_dim, (hipStream_t)stream);
 }
 
 int sfa_kv8_quantize(void *dst, const void *src, const float *scale, int64_t rows, int num_heads_kv, int head_dim,

@@ -1,5 +1,5 @@
-// The body the two matrix-core decode kernels share (decode_gqa_mfma_kernel.hip: 16-bit caches; decode_kv8_kernel.hip:
-// e4m3 caches): one workgroup per (batch, kv head, split), four waves, 32-key tiles on v_mfma_f32_16x16x32, 16 query
+// The body the matrix-core decode kernels share (decode_gqa_mfma_kernel.hip: 16-bit caches; decode_kv8_kernel.hip:
+// e4m3 caches; decode_window_kernel.hip: a sliding window over 16-bit caches): one workgroup per (batch, kv head, split), four waves, 32-key tiles on v_mfma_f32_16x16x32, 16 query
 // columns of which G are real, one online-softmax state per lane.  Lane coordinates: MFMA (c = lane & 15, g = lane >> 4);
 // prologue / row-major (sub = lane % (D/8): which 8 dims, grp = lane / (D/8): which head or row of a pass).
 // A kernel file keeps what differs: how a tile of the caches reaches the K fragments and the wave's LDS V tile, its
@@ -124,6 +124,24 @@ __device__ __forceinline__ void wave_slice(int pos, int S, int split, int wave, 
     w1 = __builtin_amdgcn_readfirstlane(min(r1, w0 + per_wave));
 }
 
+// The same over the rows [lo, pos) of a sliding window (decode_window_kernel.hip): boundaries are multiples of 32 rows
+// measured from lo & ~31, so a tile still starts on a multiple of 32 and its 16-row halves each lie in one page.  The
+// first tile may begin below lo; a wave with no row at or above lo gets the empty slice w0 == w1.  lo = 0 is the
+// partition above.
+__device__ __forceinline__ void wave_slice(int lo, int pos, int S, int split, int wave, int &w0, int &w1) {
+    const int base = lo & ~(kTile - 1);
+    int rows_per_split = (pos - base + S - 1) / S;
+    rows_per_split = (rows_per_split + kTile - 1) / kTile * kTile;
+    const int r0 = min(pos, base + split * rows_per_split);
+    const int r1 = min(pos, r0 + rows_per_split);
+    int per_wave = (r1 - r0 + kDecodeWaves - 1) / kDecodeWaves;
+    per_wave = (per_wave + kTile - 1) / kTile * kTile;
+    const int a = min(r1, r0 + wave * per_wave);
+    const int e = min(r1, a + per_wave);
+    w0 = __builtin_amdgcn_readfirstlane(e > lo ? a : e);                // wave-uniform
+    w1 = __builtin_amdgcn_readfirstlane(e);
+}
+
 // Offsets of cache rows from head_base(), in elements.  Paged: the rows 0-15 and 16-31 of a tile each lie in ONE page
 // (page_size >= 16, and see wave_slice): two scalar table look-ups per tile and a compile-time choice per load, no
 // per-lane select.  Rows past the wave's end are clamped to its last row; clamping the page INDEX the same way keeps
@@ -157,6 +175,14 @@ template <bool PAGED> struct Pages {
         const int last = (w1 - 1) >> page_shift;
         po[0] = page_of(min(t >> page_shift, last));
         po[1] = page_of(min((t + 16) >> page_shift, last));
+    }
+    // the same for a wave whose rows begin at lo (lo < w1): rows below lo are re-addressed to row lo by the caller, so
+    // page indices below lo's page are re-addressed to that page and no entry below it is looked at
+    __device__ __forceinline__ void set(int t, int lo, int w1) {
+        if (!PAGED) return;
+        const int first = lo >> page_shift, last = (w1 - 1) >> page_shift;
+        po[0] = page_of(min(max(t >> page_shift, first), last));
+        po[1] = page_of(min(max((t + 16) >> page_shift, first), last));
     }
     // a row of the tile of set(); half = which 16 rows of the tile it lies in
     __device__ __forceinline__ long long row_off(int row, int half) const {
@@ -202,8 +228,10 @@ template <class Tr, int D> struct Tiles {
         m = neg_inf(); l = 0.f;
     }
 
-    // one 32-key tile: kk = K fragments, V tile at buf, the first nvalid keys are real, scores * scale in log2 units
-    __device__ __forceinline__ void tile(const uint4 (&kk)[2][NKS], const char *buf, int nvalid, float scale) {
+    // one 32-key tile: kk = K fragments, V tile at buf, the first nvalid keys are real, scores * scale in log2 units.
+    // LOWER (a sliding window): the keys below nlo are masked as well.
+    template <bool LOWER = false>
+    __device__ __forceinline__ void tile(const uint4 (&kk)[2][NKS], const char *buf, int nvalid, float scale, int nlo = 0) {
         const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
         f32x4 s[2];
 #pragma unroll
@@ -218,7 +246,8 @@ template <class Tr, int D> struct Tiles {
         for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {       // element r of tile kt = key 16 kt + 4 g + r
-                s[kt][r] = (16 * kt + 4 * g + r < nvalid) ? s[kt][r] * scale : neg_inf();
+                const int key = 16 * kt + 4 * g + r;
+                s[kt][r] = (key < nvalid && (!LOWER || key >= nlo)) ? s[kt][r] * scale : neg_inf();
                 mx = fmaxf(mx, s[kt][r]);
             }
         mx = fmaxf(m, quad_max(mx));

@@ -13,6 +13,8 @@ libStarFlashAttention.so.  The public operators:
                       prefill / verify / decode step (new entry point).
   flash_decode_kv8(...)  flash_decode over an fp8 (e4m3) KV cache with a scale per kv head; quantize_kv8(...) moves
                       16-bit cache rows into such a cache (new entry points).
+  flash_decode_window(...)  flash_decode with a sliding window: the token attends to the last `window` positions only
+                      (new entry point).
 """
 import ctypes
 import math
@@ -148,7 +150,7 @@ def _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_
 
 
 def _call_decode(dev, a, stride, num_splits, ws, call):
-    """What the three decode operators end in: the batch stride, the split count and the workspace go into `a`,
+    """What the decode operators end in: the batch stride, the split count and the workspace go into `a`,
     call(args, stream) makes the C-ABI call and, with sync checks on, the status is polled."""
     a.stride = stride
     a.num_splits = num_splits
@@ -187,6 +189,30 @@ def flash_decode(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_
             ws = torch.empty(lib.sfa_decode_workspace_bytes(B, H, D, M, 0), dtype=torch.uint8, device=dev)
             _lib.check(lib.sfa_decode_reset_status(ctypes.c_void_p(ws.data_ptr()), _stream_ptr(dev)))
         _call_decode(dev, a, (H + 2 * Hkv) * D, S, ws, lib.sfa_decode)
+    return o
+
+
+def flash_decode_window(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o,
+                        batch_size, memory_max_len, num_heads, head_dim, rotary_embedding_dim,
+                        max_input_length, num_layer, idx_layer, window, *, num_splits=0,
+                        rotary_cos_table=None, rotary_sin_table=None, softmax_scale=None, kv_layout="blmhd",
+                        block_table=None, num_heads_kv=None):
+    """flash_decode with a sliding window (include/star_flash_attn.h, sfa_decode_window): the new token at position
+    pos = seq_len[b] attends to itself and the window - 1 cache rows before it, lo = max(0, pos + 1 - window) .. pos
+    (flash-attn's window_size = (window - 1, 0)).  window >= 1; every other argument as in flash_decode.  Cache rows
+    below lo, and block_table entries of pages wholly below lo, are never read.  Returns `o`."""
+    lib = _lib.load()
+    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
+                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
+                                      kv_layout, block_table, num_heads_kv)
+    W = int(window)
+    _require(-2 ** 31 <= W < 2 ** 31, f"window={window} does not fit an int")
+    dev = qkv.device
+    with torch.cuda.device(dev):
+        S = int(num_splits) if num_splits and num_splits > 0 else 0
+        ws = _workspace(dev, lib.sfa_decode_window_workspace_bytes(B, H, Hkv, D, M, W, S))
+        _call_decode(dev, a, (H + 2 * Hkv) * D, S, ws, lambda args, stream: lib.sfa_decode_window(args, W, stream))
     return o
 
 
