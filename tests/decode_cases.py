@@ -1,19 +1,21 @@
 """Structured decode problems for tests/test_decode_numerics_{cpu,gpu}.py, their oracle, and one adapter that runs a
-problem through any of the four decode entry points in any cache layout.
+problem through any of the five decode entry points in any cache layout.
 
 A canonical problem (class Problem) is layout-free and packed like sfa_decode_varlen's arguments:
 
   q [T, H, D], k_new / v_new [T, Hkv, D]   float32, representable in `dtype`; sequence b owns rows cu[b] .. cu[b+1]
   kc, vc [B, L, M, Hkv, D]                 the caches as STORAGE BITS: uint16 (fp16 / bf16) or uint8 (e4m3, entry "kv8")
-  lens [B], ns [B]                         cached rows and new tokens per sequence (ns = 1 for "decode" and "kv8",
-                                           one common n for "chunk", anything for "varlen")
+  lens [B], ns [B]                         cached rows and new tokens per sequence (ns = 1 for "decode", "kv8" and
+                                           "window", one common n for "chunk", anything for "varlen")
+  window, lo [B]                           entry "window": the call's window and lo[b] = max(0, pos + 1 - window), the
+                                           first row sequence b may read; else None and zeros
   ks, vs [Hkv]                             the e4m3 scales of "kv8" (powers of two, see e4m3_scales), else None
 
 The caches are kept as bits so that a problem can hold NaN patterns in the bytes the contract never reads (poisoned)
 and so that "bit-identical" and "this byte was not written" are plain array comparisons.
 
 Every sequence is described by its whole key sequence K[0 .. pos + n): rows below pos go into the cache, the rest are
-the new tokens, so one builder serves all four entry points.  All structured problems use rotary_embedding_dim = 0 and
+the new tokens, so one builder serves every entry point.  All structured problems use rotary_embedding_dim = 0 and
 no bias: the q and k the device sees are the input bits.
 """
 import ctypes
@@ -21,6 +23,7 @@ import ctypes
 import numpy as np
 
 import kv8_ref
+import window_ref
 from oracle import decode_ref, round_to
 from oracle.numerics import from_bits16, to_bits16
 
@@ -34,7 +37,7 @@ SPIKE_ROWS = [0, 1, 15, 16, 31, 32, 47, 48, 63, 64, 66, 67, 95, 96, 127, 128, 13
 
 
 class Problem:
-    def __init__(self, entry, dtype, G, D, seqs, rot=0, amax_scales=False):
+    def __init__(self, entry, dtype, G, D, seqs, rot=0, amax_scales=False, window=None):
         """seqs: dicts with pos, q [n, H, D], K / V [pos + n, Hkv, D] (float) and the builders' notes:
         hot [n] = the key row (of the sequence) that must carry the weight of token t, or -1;
         exact [n] = True where o must equal v at the hot row bit for bit; spike = the row that is 4u; ramp = +-1."""
@@ -45,8 +48,11 @@ class Problem:
         self.ns = [int(s["q"].shape[0]) for s in seqs]
         self.cu = [0] + [int(x) for x in np.cumsum(self.ns)]
         self.T = self.cu[-1]
-        assert entry in ("decode", "kv8", "chunk", "varlen")
+        assert entry in ("decode", "kv8", "chunk", "varlen", "window")
         assert entry == "varlen" or len(set(self.ns)) == 1 and (entry == "chunk" or self.ns[0] == 1)
+        assert (entry == "window") == (window is not None) and (window is None or window >= 1)
+        self.window = None if window is None else int(window)
+        self.lo = [window_ref.window_lo(pos, window) for pos in self.lens]
         assert all(p + n <= M for p, n in zip(self.lens, self.ns))
         r16 = lambda x: round_to(x, dtype).astype(np.float32) + np.float32(0.0)       # (+ 0.0: no -0.0, see to_bits)
         cat = lambda key, shape: (np.concatenate([s[key] for s in seqs]) if self.T else np.zeros(shape)).astype(np.float32)
@@ -100,10 +106,10 @@ class Problem:
 
     def unread_mask(self):
         """[B, L, M] True on every cache row the contract does not name: the other layers, and the rows of idx_layer
-        from pos + n on."""
+        from pos + n on and (a window) below lo."""
         m = np.ones((self.B, L, M), bool)
         for b in range(self.B):
-            m[b, LAYER, :self.lens[b] + self.ns[b]] = False
+            m[b, LAYER, self.lo[b]:self.lens[b] + self.ns[b]] = False
         return m
 
     def poisoned(self, pattern=None):
@@ -136,10 +142,19 @@ def e4m3_scales(arrays, doubled):
 # the oracle
 # ---------------------------------------------------------------------------------------------------------------------
 
-def oracle(p, scale=None):
+def oracle(p, scale=None, window=None):
     """fp64 reference of the whole call: dict(o [T, H, D] float32 unrounded, kc, vc = the caches afterwards, as bits).
-    16-bit entries: oracle.decode_ref token by token per sequence; kv8: kv8_ref.decode_kv8_ref."""
+    16-bit entries: oracle.decode_ref token by token per sequence; kv8: kv8_ref.decode_kv8_ref; window:
+    window_ref.decode_window_ref, which looks at the rows [lo, pos] only (window=: another window than the problem's)."""
     kc, vc = p.kc.copy(), p.vc.copy()
+    if p.entry == "window":
+        layer = lambda c: from_bits16(c[:, LAYER:LAYER + 1], p.dtype)                    # [B, 1, M, Hkv, D]
+        ref = window_ref.decode_window_ref(p.q, p.k_new, p.v_new, layer(kc), layer(vc), p.lens, 0, p.rot,
+                                           p.window if window is None else window, p.dtype, scale=scale)
+        for b, pos in enumerate(p.lens):
+            kc[b, LAYER, pos] = to_bits16(ref["k_row"][b], p.dtype)
+            vc[b, LAYER, pos] = to_bits16(ref["v_row"][b], p.dtype)
+        return dict(o=ref["o"], kc=kc, vc=vc)
     o = np.zeros((p.T, p.H, p.D), np.float32)
     G = p.G
     if p.entry == "kv8":
@@ -164,13 +179,15 @@ def oracle(p, scale=None):
 
 def scores_log2(p, ref, r, scale=None, causal=True):
     """[H, pos + n] the scores of packed token r in log2 units over its sequence's keys (from the caches after the call,
-    `ref` = oracle(p)); keys the token must not see are -inf unless causal=False."""
+    `ref` = oracle(p)); keys the token must not see (later tokens; a window: the rows below lo) are -inf unless
+    causal=False."""
     b, t = p.seq_of(r)
     pos, n = p.lens[b], p.ns[b]
     K = np.repeat(p.values(ref["kc"][b, LAYER, :pos + n], p.ks), p.G, axis=1)               # [pos + n, H, D]
     sc = np.einsum("hd,thd->ht", p.q[r].astype(np.float64), K) * (p.D ** -0.5 if scale is None else scale) * np.log2(np.e)
     if causal:
         sc[:, pos + t + 1:] = -np.inf
+        sc[:, :p.lo[b]] = -np.inf
     return sc
 
 
@@ -274,15 +291,93 @@ def seq_normal(seed, G, D, pos, n=1, e4m3=False):
                 V=rng.standard_normal((pos + n, HKV, D)))
 
 
+# ---- the edges of a sliding window (entry "window"): one sequence per lo, pos = lo + window - 1, so that every cached row
+# from lo on is inside the window and row lo - 1 is the first one outside ----
+
+WINDOWS = (17, 32, 40, 100)
+WINDOW_LOS = [0, 1, 15, 16, 17, 31, 32, 33, 48, 63, 64, 65, 96, 127, 128, 129, 156]
+EDGE_KINDS = ["edge_in", "edge_last", "edge_out", "ramp_through", "equal"]
+STRESS_WINDOW = 40                               # the window of sections A (the kinds it shares), B and C
+UNREAD_WINDOWS = (40, 16, 1)                     # section C: 16 = a window that begins on a page boundary at pos 15, 31,
+#                                                  63; 1 = no cached row is read at all, lo = pos on no tile boundary
+
+
+def equal_magnitude(window):
+    """|V| of the marked rows of seq_window_equal: a one-row error moves o by about A / window, which must clear 5 times
+    the tolerance of bf16 (tests/test_decode_numerics_cpu.py, test_window_equal_marks_every_one_row_error)"""
+    return 8.0 if window <= 40 else 32.0
+
+
+def seq_window_edge(seed, G, D, lo, window, where):
+    """K[row] = 4u among 0.25 N(0,1) keys.  where "in": row = lo, the first row of the window; "last": row = pos - 1, the
+    last cached row; "out": row = lo - 1, the last row below the window -- finite, and nobody may see it."""
+    pos = lo + window - 1
+    row = {"in": lo, "last": pos - 1, "out": lo - 1}[where]
+    assert 0 <= row < pos
+    rng = _rng(seed, G, D, lo, window, row)
+    u, q, K, V = _frame(rng, G, D, pos, 1, False)
+    K[row] = 4.0 * u
+    return dict(pos=pos, q=q, K=K, V=V, hot=[-1 if where == "out" else row], spike=row)
+
+
+def seq_window_ramp(seed, G, D, lo, window, through):
+    """through: K[r] = 4 (pos - r) / window * u for EVERY row r <= pos, so that the largest score of the window is at row
+    lo and every row below lo would beat it.  Else the ascending ramp K[r] = 4 (r - lo) / (window - 1) * u over [lo, pos]
+    (the running max moves in every tile of the window) above rows of zeros."""
+    pos = lo + window - 1
+    rng = _rng(seed, G, D, lo, window, through)
+    u, q, K, V = _frame(rng, G, D, pos, 1, False)
+    r = np.arange(pos + 1, dtype=np.float64)
+    f = 4.0 * (pos - r) / window if through else 4.0 * np.maximum(r - lo, 0.0) / (window - 1)
+    K = f[:, None, None] * u[None]
+    return dict(pos=pos, q=q, K=K, V=V, ramp=-1 if through else 1)
+
+
+def seq_window_equal(seed, G, D, lo, window):
+    """every key of the sequence = u, below the window as well, V = N(0,1): o = the mean of V over exactly the rows
+    lo .. pos.  Rows lo - 1, lo and pos - 1 of V are +-A (a sign per element, A = equal_magnitude(window)), so that each
+    one-row error -- row lo dropped, row lo counted twice, row lo - 1 added, row pos - 1 dropped -- moves o by ~A / window."""
+    pos = lo + window - 1
+    rng = _rng(seed, G, D, lo, window)
+    u, q, K, V = _frame(rng, G, D, pos, 1, False)
+    K = np.broadcast_to(u, K.shape).copy()
+    for row in (lo - 1, lo, pos - 1):
+        if row >= 0:
+            V[row] = equal_magnitude(window) * rng.choice([-1.0, 1.0], size=V[row].shape)
+    return dict(pos=pos, q=q, K=K, V=V)
+
+
+def window_los(window, kind):
+    """the lo of each sequence of a window-edge batch: pos = lo + window - 1 stays below M; edge_out needs a row lo - 1"""
+    return [lo for lo in WINDOW_LOS if lo + window - 1 <= M - 1 and (kind != "edge_out" or lo >= 1)]
+
+
+def window_edges(dtype, G, D, kind, window):
+    """The window-edge problems: one batch per (kind, window), a sequence per lo (ramp_through: two, the ramp that goes
+    on below lo and the ascending one)."""
+    kw = dict(G=G, D=D, window=window)
+    los = window_los(window, kind)
+    if kind in ("edge_in", "edge_last", "edge_out"):
+        seqs = [seq_window_edge(500 + i, lo=lo, where=kind[5:], **kw) for i, lo in enumerate(los)]
+    elif kind == "ramp_through":
+        seqs = [seq_window_ramp(600 + i, lo=lo, through=t, **kw) for i, lo in enumerate(los) for t in (True, False)]
+    elif kind == "equal":
+        seqs = [seq_window_equal(700 + i, lo=lo, **kw) for i, lo in enumerate(los)]
+    else:
+        raise ValueError(kind)
+    return Problem("window", dtype, G, D, seqs, window=window)
+
+
 VARLEN_NS = [1, 3, 40, 0, 17]
 CHUNK_SPIKES = [(pos, j) for pos in (0, 30, 100) for j in (0, 1, 31, 32, 39)]     # n = 40
 
 
 def softmax_stress(entry, dtype, G, D, kind):
-    """The problems of section A, one batch per kind: a sequence per case."""
+    """The problems of section A, one batch per kind: a sequence per case.  Entry "window": at window STRESS_WINDOW."""
     e = entry == "kv8"
     kw = dict(G=G, D=D, e4m3=e)
-    n = {"decode": 1, "kv8": 1, "chunk": 5}.get(entry)
+    n = {"decode": 1, "kv8": 1, "chunk": 5, "window": 1}.get(entry)
+    window = STRESS_WINDOW if entry == "window" else None
     if entry == "varlen":
         ns = VARLEN_NS
         if kind == "spike":
@@ -314,12 +409,14 @@ def softmax_stress(entry, dtype, G, D, kind):
         seqs = [seq_extreme(i, pos=pos, n=n, **kw) for i, pos in enumerate([200, 255 if n == 1 else 256 - n, 33])]
     else:
         raise ValueError(kind)
-    return Problem(entry, dtype, G, D, seqs)
+    return Problem(entry, dtype, G, D, seqs, window=window)
 
 
 def stress_kinds(entry):
     if entry == "varlen":
         return ["spike", "ramp", "extreme"]
+    if entry == "window":                       # its spikes, ramps and equal keys are the window-edge problems
+        return ["below", "extreme"]
     return ["spike", "ramp", "equal", "below", "extreme"] + (["chunk_spike"] if entry == "chunk" else [])
 
 
@@ -328,9 +425,12 @@ UNREAD_CHUNK_POS = [0, 19, 51, 52, 115, 200]                   # n = 13: pos + n
 VARLEN_POS = [200, 30, 100, 50, 0]
 
 
-def normal_problem(entry, dtype, G, D, rot=0, stale=False, amax_scales=False):
+def normal_problem(entry, dtype, G, D, rot=0, stale=False, amax_scales=False, window=None):
     """N(0,1) data at the positions of section C (also section B's problem).  stale: the batch of the stale-workspace
-    case instead: it contains pos = 0, and a sequence without tokens for varlen."""
+    case instead: it contains pos = 0, and a sequence without tokens for varlen.  Entry "window": at `window`
+    (STRESS_WINDOW if None)."""
+    if entry == "window" and window is None:
+        window = STRESS_WINDOW
     kw = dict(G=G, D=D)
     if entry == "varlen":
         seqs = [seq_normal(i, pos=pos, n=n, **kw) for i, (pos, n) in enumerate(zip(VARLEN_POS, VARLEN_NS))]
@@ -338,7 +438,7 @@ def normal_problem(entry, dtype, G, D, rot=0, stale=False, amax_scales=False):
         seqs = [seq_normal(i, pos=pos, n=13, **kw) for i, pos in enumerate([0, 5, 200] if stale else UNREAD_CHUNK_POS)]
     else:
         seqs = [seq_normal(i, pos=pos, **kw) for i, pos in enumerate([0, 2, 129] if stale else UNREAD_POS)]
-    return Problem(entry, dtype, G, D, seqs, rot=rot, amax_scales=amax_scales)
+    return Problem(entry, dtype, G, D, seqs, rot=rot, amax_scales=amax_scales, window=window)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -372,6 +472,14 @@ def _configs():
                 for layout in ("blmhd", "paged"):
                     c.append((entry, G, D, layout, ("fp16", "bf16")[(i + (D == 128)) % 2], {}))
                     i += 1
+    # the sliding window (decode_window_kernel.hip): one matrix-core kernel for every group size, G = 1 and 2 on padded
+    # query columns; blhmd = operand-layout loads, blmhd = row-major, paged.  Every (head_dim, layout) pair, every G
+    # three times (G = 1 and 2 on each load path), non-temporal loads forced once per load path.
+    shapes = [(64, "blhmd"), (64, "blmhd"), (64, "paged"), (128, "blhmd"), (128, "blmhd"), (128, "paged"),
+              (256, "blhmd"), (256, "blmhd"), (256, "paged"), (128, "paged"), (64, "blmhd"), (128, "paged"),
+              (256, "paged"), (128, "blmhd"), (64, "blhmd")]
+    for i, (D, layout) in enumerate(shapes):
+        c.append(("window", (1, 2, 4, 8, 16)[i % 5], D, layout, ("bf16", "fp16")[i % 2], {"decode_nt": 1} if i in (1, 5, 6) else {}))
     return c
 
 
@@ -394,12 +502,15 @@ def page_table(B):
     return np.random.default_rng(3).permutation(num_pages)[:B * pps].astype(np.int32).reshape(B, pps), num_pages
 
 
-def call_table(p, table, beyond=None):
-    """the table a call gets: `beyond` (e.g. -1) in every entry past the last page a sequence needs"""
+def call_table(p, table, beyond=None, below=None):
+    """the table a call gets: `beyond` (e.g. -1) in every entry past the last page a sequence needs, `below` in every
+    entry of a page that lies wholly below lo (a window), that is entries [0, lo // PS)"""
     t = table.copy()
-    if beyond is not None:
-        for b in range(p.B):
+    for b in range(p.B):
+        if beyond is not None:
             t[b, p.pages_needed(b):] = beyond
+        if below is not None:
+            t[b, :p.lo[b] // PS] = below
     return t
 
 
@@ -407,7 +518,7 @@ class Run:
     """The device side of one problem in one layout.  .call(...) makes the operator call; .result() brings o and the
     caches back in canonical form (bits)."""
 
-    def __init__(self, p, layout, table_beyond=None):
+    def __init__(self, p, layout, table_beyond=None, table_below=None):
         import torch
         self.torch, self.p, self.layout = torch, p, layout
         self.dev = dev = torch.device("cuda:0")
@@ -415,7 +526,7 @@ class Run:
         self.table = self.num_pages = self.block_table = None
         if layout == "paged":
             self.table, self.num_pages = page_table(p.B)
-            self.block_table = torch.from_numpy(call_table(p, self.table, table_beyond)).to(dev)
+            self.block_table = torch.from_numpy(call_table(p, self.table, table_beyond, table_below)).to(dev)
         self.kc, self.vc = self._to_layout(p.kc), self._to_layout(p.vc)
         t16 = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(self.tdt).to(dev)
         H, Hkv, D = p.H, p.Hkv, p.D
@@ -490,6 +601,8 @@ class Run:
         kw = self.keywords(num_splits, softmax_scale)
         if p.entry == "varlen":
             ret = sfa.flash_decode_varlen(self.qkv, None, None, None, kc, vc, sl, o, self.cu, *sizes, **kw)
+        elif p.entry == "window":
+            ret = sfa.flash_decode_window(self.qkv, None, None, None, kc, vc, sl, o, *sizes, p.window, **kw)
         else:
             fn = {"decode": sfa.flash_decode, "kv8": sfa.flash_decode_kv8, "chunk": sfa.flash_decode_chunk}[p.entry]
             ret = fn(self.qkv, None, None, None, kc, vc, sl, o, *sizes, **kw)
@@ -537,13 +650,13 @@ class Run:
         return dict(o=o, kc=kc, vc=vc, spare_k=sk, spare_v=sv)
 
 
-def run(sfa, p, layout, num_splits=0, softmax_scale=None, table_beyond=None, knobs=None):
+def run(sfa, p, layout, num_splits=0, softmax_scale=None, table_beyond=None, knobs=None, table_below=None):
     """One call of p's entry point on fresh device copies; the debug knobs are set for the call and restored."""
     knobs = knobs or {}
     for k, v in knobs.items():
         sfa.debug_set(k, v)
     try:
-        res = Run(p, layout, table_beyond).call(sfa, num_splits, softmax_scale).result()
+        res = Run(p, layout, table_beyond, table_below).call(sfa, num_splits, softmax_scale).result()
     finally:
         for k in knobs:
             sfa.debug_set(k, -1)

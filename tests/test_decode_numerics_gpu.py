@@ -1,11 +1,15 @@
-"""Adversarial numerics of the four decode entry points (sfa_decode and its three kernels, sfa_decode_kv8,
-sfa_decode_chunk, sfa_decode_varlen) against the fp64 oracle, on the problems of tests/decode_cases.py:
+"""Adversarial numerics of the five decode entry points (sfa_decode and its three kernels, sfa_decode_kv8,
+sfa_decode_chunk, sfa_decode_varlen, sfa_decode_window) against the fp64 oracle, on the problems of
+tests/decode_cases.py:
 
   A  softmax stress: a dominating key in a chosen tile / wave share / split, among the new tokens, nowhere; running
      maxima that move in every tile or never; all keys equal; all scores far below zero; logits in the hundreds
+  W  the edges of a sliding window: the same structures placed on the first row of the window, on its last cached row
+     and on the row just below it, for every alignment of lo to the 32-row tile, its 16-row halves and the pages
   B  softmax_scale (head_dim_inv of the C ABI), which no other decode test passes
   C  what the kernels must not read: NaN / Inf bit patterns in every cache byte outside rows 0 .. pos + n - 1 of
-     idx_layer, -1 in the block_table entries past a sequence's last page, NaN in the workspace
+     idx_layer (a window: outside rows lo .. pos), -1 in the block_table entries past a sequence's last page (and of the
+     pages wholly below lo), NaN in the workspace
 
 Tolerances are the project's (tests/test_decode_gpu.py): kernel against fp64 on identical inputs, atol = rtol = 2e-3
 (fp16) / 1.6e-2 (bf16), elementwise, nothing exempt.  Sections A and C run with rotary_embedding_dim = 0 and no bias, so
@@ -53,6 +57,13 @@ def stress(entry, dtype, G, D, kind):
     return cached(("A", entry, dtype, G, D, kind), make)
 
 
+def edges(dtype, G, D, kind, window):
+    def make():
+        p = dc.window_edges(dtype, G, D, kind, window)
+        return p, dc.oracle(p)
+    return cached(("W", dtype, G, D, kind, window), make)
+
+
 def assert_close(p, res, ref, what):
     o = from_bits16(res["o"], p.dtype)
     assert np.isfinite(o).all(), what
@@ -94,13 +105,41 @@ def test_softmax_stress(sfa, cfg, kind):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# W. the edges of a sliding window
+# ---------------------------------------------------------------------------------------------------------------------
+
+_WINDOW_CONFIGS = [c for c in dc.CONFIGS if c[0] == "window"]
+
+
+@pytest.mark.parametrize("window", dc.WINDOWS, ids=lambda w: f"w{w}")
+@pytest.mark.parametrize("kind", dc.EDGE_KINDS)
+@pytest.mark.parametrize("cfg", _WINDOW_CONFIGS, ids=dc.config_id)
+def test_window_edges(sfa, cfg, kind, window):
+    """One batch per (kind, window), a sequence per lo with pos = lo + window - 1 (decode_cases.window_edges): a key that
+    carries all the weight on row lo or on row pos - 1; one just as large on row lo - 1, which nobody may see; a ramp that
+    peaks at lo and goes on rising below it, and one that rises in every tile of the window; all keys equal with rows
+    lo - 1, lo and pos - 1 of V so large that one row dropped, added or counted twice is far outside the tolerance
+    (tests/test_decode_numerics_cpu.py).  At num_splits 1, 3 and 4 (window 17: splits and waves without rows): o against
+    the oracle, elementwise; the appended rows and every other cache byte; a clean status."""
+    entry, G, D, layout, dtype, knobs = cfg
+    p, ref = edges(dtype, G, D, kind, window)
+    for S in (1, 3, 4):
+        what = (dc.config_id(cfg), kind, f"window={window}", f"num_splits={S}")
+        res = dc.run(sfa, p, layout, S, knobs=knobs)
+        sfa.check_decode_status()
+        assert_close(p, res, ref, what)
+        assert_caches(p, res, ref, what)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # B. softmax_scale
 # ---------------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("cfg", dc.CONFIGS, ids=dc.config_id)
 def test_softmax_scale(sfa, cfg):
-    """N(0,1) data (rotation on for the 16-bit caches; kv8 with k_scale = amax / 448 times [0.5, 2.0] per head) at
-    softmax_scale 0.03 and 0.5 against the oracle with scale=; the call without the argument gives another result."""
+    """N(0,1) data (rotation on for the 16-bit caches; kv8 with k_scale = amax / 448 times [0.5, 2.0] per head; the
+    window: 40) at softmax_scale 0.03 and 0.5 against the oracle with scale=; the call without the argument gives
+    another result."""
     entry, G, D, layout, dtype, knobs = cfg
     p = cached(("B", entry, dtype, G, D), lambda: dc.normal_problem(entry, dtype, G, D, rot=0 if entry == "kv8" else D,
                                                                     amax_scales=True))
@@ -124,6 +163,8 @@ def test_softmax_scale(sfa, cfg):
 
 _UNREAD = ([(c, "nan") for c in dc.CONFIGS] + [(c, "inf") for c in dc.CONFIGS if c[0] != "kv8"] +
            [(c, "nan_table-1") for c in dc.CONFIGS if c[3] == "paged"])
+# the window: each mode at every window of decode_cases.UNREAD_WINDOWS; "nan" is window 40, "nan_w16" window 16, ...
+_UNREAD += [(c, f"{mode}_w{w}") for c, mode in _UNREAD if c[0] == "window" for w in dc.UNREAD_WINDOWS[1:]]
 
 
 @pytest.mark.parametrize("cfg,mode", _UNREAD, ids=lambda x: x if isinstance(x, str) else dc.config_id(x))
@@ -131,17 +172,24 @@ def test_unread_memory_is_not_read(sfa, cfg, mode):
     """The same call on a clean problem (zeros in every cache byte the contract does not name) and on a poisoned one (NaN
     patterns there -- 0x7FFF, e4m3 0x7F -- or +Inf; in the pages nobody owns as well; "table-1": and -1 in the block_table
     entries past the last page a sequence needs): o and the appended rows bit-identical, the status clean, every poisoned
-    byte still in place.  num_splits 4 leaves splits without keys at the small positions."""
+    byte still in place.  num_splits 4 leaves splits without keys at the small positions.
+    A window: the rows below lo are poisoned as well (in the clean problem they hold the sequence's data), "table-1" also
+    puts -1 into the entries of the pages wholly below lo, and "_w16" / "_w1" run window 16 (at pos = 15, 31, 63 the window
+    begins exactly on a page boundary) and window 1 (no cached row is read; lo = pos, mostly on no tile boundary)
+    instead of 40."""
     entry, G, D, layout, dtype, knobs = cfg
-    clean = cached(("C", entry, dtype, G, D), lambda: dc.normal_problem(entry, dtype, G, D))
-    ref = cached(("C", entry, dtype, G, D, "oracle"), lambda: dc.oracle(clean))
+    mode, _, window = mode.partition("_w")
+    window = (int(window) if window else dc.STRESS_WINDOW) if entry == "window" else None
+    clean = cached(("C", entry, dtype, G, D, window), lambda: dc.normal_problem(entry, dtype, G, D, window=window))
+    ref = cached(("C", entry, dtype, G, D, window, "oracle"), lambda: dc.oracle(clean))
     bad = clean.poisoned(dc.INF16[dtype] if mode == "inf" else None)
     m = clean.unread_mask()
     for S in (1, 3, 4):
         what = (dc.config_id(cfg), mode, f"num_splits={S}")
         a = dc.run(sfa, clean, layout, S, knobs=knobs)
         sfa.check_decode_status()
-        z = dc.run(sfa, bad, layout, S, table_beyond=-1 if mode.endswith("table-1") else None, knobs=knobs)
+        minus = -1 if mode.endswith("table-1") else None
+        z = dc.run(sfa, bad, layout, S, table_beyond=minus, table_below=minus, knobs=knobs)
         sfa.check_decode_status()                                           # clean, the -1 entries included
         assert np.isfinite(from_bits16(z["o"], dtype)).all(), what
         np.testing.assert_array_equal(z["o"], a["o"], err_msg=f"{what}: o depends on bytes outside the contract")
