@@ -1,9 +1,10 @@
-// The body the matrix-core decode kernels share (decode_gqa_mfma_kernel.hip: 16-bit caches; decode_kv8_kernel.hip:
-// e4m3 caches; decode_window_kernel.hip: a sliding window over 16-bit caches): one workgroup per (batch, kv head, split), four waves, 32-key tiles on v_mfma_f32_16x16x32, 16 query
+// What the matrix-core decode kernels share whatever the cache's element type (decode_mfma16.h: the 16-bit caches of
+// decode_gqa_mfma_kernel.hip and, with a sliding window, decode_window_kernel.hip; decode_kv8_kernel.hip: e4m3 caches): one
+// workgroup per (batch, kv head, split), four waves, 32-key tiles on v_mfma_f32_16x16x32, 16 query
 // columns of which G are real, one online-softmax state per lane.  Lane coordinates: MFMA (c = lane & 15, g = lane >> 4);
 // prologue / row-major (sub = lane % (D/8): which 8 dims, grp = lane / (D/8): which head or row of a pass).
-// A kernel file keeps what differs: how a tile of the caches reaches the K fragments and the wave's LDS V tile, its
-// software pipeline, and the append store.  The design is described in decode_gqa_mfma_kernel.hip.
+// decode_mfma16.h and decode_kv8_kernel.hip keep what differs: how a tile of the caches reaches the K fragments and the
+// wave's LDS V tile, the software pipeline, and the append store.  The design is described in decode_gqa_mfma_kernel.hip.
 #pragma once
 #include "decode_common.h"
 

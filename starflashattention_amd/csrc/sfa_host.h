@@ -79,7 +79,8 @@ struct Kv8KernelParams {
     const float *k_scale, *v_scale;     // [Hkv] each, nullptr = 1.0
 };
 
-// sfa_decode_window (decode_window_kernel.hip): sfa_decode over the last `window` positions.
+// sfa_decode_window (decode_window_kernel.hip, the body of decode_mfma16.h with its window): sfa_decode over the last
+// `window` positions.
 struct WindowKernelParams {
     DecodeKernelParams d;   // every field keeps its sfa_decode meaning
     int window;             // >= 1: the token at pos attends to the rows max(0, pos + 1 - window) .. pos
@@ -114,7 +115,8 @@ int launch_decode_kv8(const Kv8KernelParams &p, int dtype, int head_dim, hipStre
 int launch_kv8_quantize(void *dst, const void *src, const float *scale, long long rows, int Hkv, int head_dim,
                         long long src_row, long long src_head, long long dst_row, long long dst_head, int dtype,
                         hipStream_t stream);
-// decode_window_kernel.hip: the sliding-window attention kernel (every group size) plus the split combine
+// decode_window_kernel.hip: the sliding-window attention kernel (every group size; one body with launch_decode_gqa_mfma's
+// kernel, decode_mfma16.h) plus the split combine
 int launch_decode_window(const WindowKernelParams &p, int dtype, int head_dim, hipStream_t stream);
 int launch_prefill(const PrefillKernelParams &p, int dtype, int head_dim, bool causal, hipStream_t stream);
 int launch_prefill_no_keys(const PrefillKernelParams &p, int head_dim, hipStream_t stream);

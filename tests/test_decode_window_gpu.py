@@ -259,14 +259,25 @@ def test_window_beyond_every_position_is_plain_decode(sfa, G):
         assert torch.equal(r.kc, full.kc) and torch.equal(r.vc, full.vc)
 
 
-@pytest.mark.parametrize("dtype", ["fp16", "bf16"])
-@pytest.mark.parametrize("layout", ["blmhd", "paged16"])
-@pytest.mark.parametrize("num_splits", [1, 3])
-def test_window_bit_identical_to_decode_where_it_does_not_bind(sfa, dtype, layout, num_splits):
-    """G = 8 at head_dim 128 is served by decode_gqa_mfma_kernel in sfa_decode: the same tile math, and with lo = 0 the
-    same tile partition"""
-    full = run(sfa, dtype, 128, 8, layout, None, num_splits)
-    r = run(sfa, dtype, 128, 8, layout, 5000, num_splits)
+# the (head_dim, G) pairs sfa_decode sends to decode_gqa_mfma_kernel without a knob (decode_dispatch.hip), on each of its
+# load paths: blmhd row-major through the K tile, blhmd in operand layout, paged
+MFMA_PAIRS = [(128, 8), (128, 4), (128, 16), (64, 8), (256, 8)]
+IDENTITY_CASES = [(D, G, num_splits, layout, dtype) for D, G in MFMA_PAIRS for dtype in ("fp16", "bf16")
+                  for layout in ("blmhd", "blhmd", "paged16") for num_splits in (1, 3)]
+
+
+def _identity_id(case):
+    D, G, *rest = case
+    return "-".join(str(x) for x in rest) + ("" if (D, G) == MFMA_PAIRS[0] else f"-D{D}-G{G}")
+
+
+@pytest.mark.parametrize("case", IDENTITY_CASES, ids=_identity_id)
+def test_window_bit_identical_to_decode_where_it_does_not_bind(sfa, case):
+    """These groups are served by decode_gqa_mfma_kernel in sfa_decode: the same body (decode_mfma16.h), and with lo = 0
+    the same tile partition"""
+    D, G, num_splits, layout, dtype = case
+    full = run(sfa, dtype, D, G, layout, None, num_splits)
+    r = run(sfa, dtype, D, G, layout, 5000, num_splits)
     sfa.check_decode_status()
     assert torch.equal(r.o, full.o)
     assert torch.equal(r.kc, full.kc) and torch.equal(r.vc, full.vc)
