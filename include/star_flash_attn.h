@@ -23,6 +23,7 @@
  *   sfa_decode_kv8              <- (no reference function: sfa_decode over an fp8 (e4m3) KV cache)
  *   sfa_kv8_quantize            <- (no reference function: 16-bit cache rows -> fp8 cache rows)
  *   sfa_decode_window           <- (no reference function: sfa_decode over the last `window` positions)
+ *   sfa_decode_chunk_window     <- (no reference function: sfa_decode_chunk / sfa_decode_varlen with that window)
  * The Python-facing mha_fwd_cuda (src/flash_api.cpp:42-68) and the C++ template
  * surface (src/flash_attn.h) in this repo are thin layers over these symbols.
  */
@@ -46,7 +47,9 @@ extern "C" {
  *      sfa_decode_kv8 and sfa_kv8_quantize (fp8 KV cache) added under the same version, beside an unchanged
  *      sfa_decode_args: callers detect these entry points by symbol
  *      sfa_decode_window and sfa_decode_window_workspace_bytes (sliding-window decode) added under the same version,
- *      beside an unchanged sfa_decode_args: callers detect them by symbol */
+ *      beside an unchanged sfa_decode_args: callers detect them by symbol
+ *      sfa_decode_chunk_window, sfa_decode_varlen_window and their _workspace_bytes functions (the sliding window in the
+ *      multi-token calls) added under the same version, in the same way */
 #define SFA_ABI_VERSION 4
 
 typedef enum sfa_status {
@@ -307,6 +310,44 @@ int sfa_kv8_quantize(void *dst, const void *src, const float *scale, int64_t row
 int    sfa_decode_window(const sfa_decode_args *args, int window, void *stream);
 size_t sfa_decode_window_workspace_bytes(int batch_size, int num_heads, int num_heads_kv, int head_dim,
                                          int memory_max_len, int window, int num_splits);
+
+/* ---- multi-token decode with a sliding window -------------------------------------- */
+/*
+ * sfa_decode_chunk / sfa_decode_varlen for a sliding-window attention layer: the call gives exactly what n successive
+ * sfa_decode_window calls would.  Everything of sfa_decode_chunk / sfa_decode_varlen holds unchanged: bias, RoPE at
+ * pos + t, the append of all n rows, every kv_layout, grouped queries, fp16 / bf16, head_dim 64 / 128 (256 returns
+ * SFA_ERR_UNSUPPORTED_HEAD_DIM), the cu_tokens rules, the rejection rules and the status word.  The only difference is
+ * the key range: token t of a sequence at pos = seq_len[b] attends to the rows [lo_t, pos + t], with
+ *   lo_t = max(0, pos + t + 1 - window).
+ *   window >= 1     window < 1 returns SFA_ERR_BAD_SHAPE.  window = 1 leaves each token its own row only; when
+ *                   window >= pos + n for every sequence the call is the plain chunk / varlen call, bit for bit.
+ * What the window promises, with lo_0 = max(0, pos + 1 - window), the lower bound of the sequence's first token, and n
+ * the sequence's token count:
+ *   - cache rows below lo_0 are never read and may hold anything (as do the rows from pos + n on and the other layers);
+ *   - in a paged cache the block_table entries [0, lo_0 / page_size) are never read and may hold any value, -1
+ *     included: a server may free the pages wholly below the window before a multi-token step as well;
+ *   - only a bad entry on a page that intersects [lo_0, pos + n) raises SFA_ERR_BLOCK_TABLE_RANGE, under the chunk
+ *     call's two rules: on a page that covers new rows it rejects the sequence, on a page that is only read it makes
+ *     the affected outputs NaN;
+ *   - lo is computed on the device from seq_len (and cu_tokens): the call allocates nothing, never synchronises and may
+ *     be captured in a graph and replayed with other contents.
+ * Workspace: layout and status word are those of the chunk / varlen call.  With num_splits <= 0 the split count is that
+ * call's own rule with min(memory_max_len, window - 1 + count) in place of memory_max_len, count = num_tokens /
+ * total_tokens: the most rows a sequence can read, so a short window is not split into slivers.  The _workspace_bytes
+ * functions size for that count.  The rule never grows with that argument, so a workspace sized by
+ * sfa_decode_chunk_workspace_bytes / sfa_decode_varlen_workspace_bytes is never too small; one that holds fewer splits
+ * than the library would pick gets the largest count it holds.  The split key range is the tiles that hold
+ * [lo_0, pos + n), not [0, pos + n): a short window over a long history is shared by all splits.
+ * Not served: an fp8 cache, head_dim 256, ring-buffer caches, attention sinks, soft-capping.
+ */
+int    sfa_decode_chunk_window(const sfa_decode_args *args, int num_tokens, int64_t qkv_token_stride, int window,
+                               void *stream);
+size_t sfa_decode_chunk_window_workspace_bytes(int batch_size, int num_heads, int num_heads_kv, int head_dim,
+                                               int memory_max_len, int num_tokens, int window, int num_splits);
+int    sfa_decode_varlen_window(const sfa_decode_args *args, const void *cu_tokens, int total_tokens,
+                                int64_t qkv_token_stride, int window, void *stream);
+size_t sfa_decode_varlen_window_workspace_bytes(int batch_size, int num_heads, int num_heads_kv, int head_dim,
+                                                int memory_max_len, int total_tokens, int window, int num_splits);
 
 /* ---- prefill: O = softmax(mask(Q K^T * scale)) V ------------------------------- */
 /*

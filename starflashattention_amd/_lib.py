@@ -26,6 +26,8 @@ EXPORTED_SYMBOLS = [
     "sfa_decode_varlen", "sfa_decode_varlen_workspace_bytes",
     "sfa_decode_kv8", "sfa_kv8_quantize",
     "sfa_decode_window", "sfa_decode_window_workspace_bytes",
+    "sfa_decode_chunk_window", "sfa_decode_chunk_window_workspace_bytes",
+    "sfa_decode_varlen_window", "sfa_decode_varlen_window_workspace_bytes",
 ]
 
 
@@ -118,6 +120,16 @@ def load():
     lib.sfa_decode_window.argtypes = [ctypes.POINTER(DecodeArgs), ctypes.c_int, ctypes.c_void_p]
     lib.sfa_decode_window_workspace_bytes.restype = ctypes.c_size_t
     lib.sfa_decode_window_workspace_bytes.argtypes = [ctypes.c_int] * 7
+    lib.sfa_decode_chunk_window.restype = ctypes.c_int
+    lib.sfa_decode_chunk_window.argtypes = [ctypes.POINTER(DecodeArgs), ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+                                            ctypes.c_void_p]
+    lib.sfa_decode_chunk_window_workspace_bytes.restype = ctypes.c_size_t
+    lib.sfa_decode_chunk_window_workspace_bytes.argtypes = [ctypes.c_int] * 8
+    lib.sfa_decode_varlen_window.restype = ctypes.c_int
+    lib.sfa_decode_varlen_window.argtypes = [ctypes.POINTER(DecodeArgs), ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
+                                             ctypes.c_int, ctypes.c_void_p]
+    lib.sfa_decode_varlen_window_workspace_bytes.restype = ctypes.c_size_t
+    lib.sfa_decode_varlen_window_workspace_bytes.argtypes = [ctypes.c_int] * 8
     lib.sfa_prefill_fwd.restype = ctypes.c_int
     lib.sfa_prefill_fwd.argtypes = [ctypes.POINTER(PrefillArgs), ctypes.c_void_p]
     lib.sfa_compute_rotary_table.restype = ctypes.c_int

@@ -142,6 +142,8 @@ constexpr EntryPoint kVarlen = {"sfa_decode_varlen", "total_tokens", false, true
 // (head_dim 256 passes the shared checks and is refused by sfa_decode_kv8 itself, with a message of its own)
 constexpr EntryPoint kKv8 = {"sfa_decode_kv8", "num_tokens", true, false, false};
 constexpr EntryPoint kWindow = {"sfa_decode_window", "num_tokens", true, false, false};
+constexpr EntryPoint kChunkWindow = {"sfa_decode_chunk_window", "num_tokens", false, true, false};
+constexpr EntryPoint kVarlenWindow = {"sfa_decode_varlen_window", "total_tokens", false, true, true};
 
 // What the entry points check alike, before any HIP call, and what they derive on the way.  sfa_decode is the case of
 // one token per sequence (count = 1) with no token stride.
@@ -466,16 +468,9 @@ size_t sfa_decode_chunk_workspace_bytes(int batch_size, int num_heads, int num_h
     return chunk_workspace(batch_size, hkv, rows, S, head_dim).total;
 }
 
-int sfa_decode_chunk(const sfa_decode_args *a, int num_tokens, int64_t qkv_token_stride, void *stream) {
-    DecodeCall dc;
-    if (const int rc = validate_decode_call(kChunk, a, num_tokens, qkv_token_stride, &dc)) return rc;
-    if (a->batch_size == 0 || num_tokens == 0) return SFA_OK;
-
-    const int rows = num_tokens * dc.group;
-    const int S = a->num_splits > 0 ? a->num_splits : chunk_auto_splits(a->batch_size, dc.hkv, rows, a->memory_max_len);
-    const DecodeWorkspace w = chunk_workspace(a->batch_size, dc.hkv, rows, S, a->head_dim);
-    if (const int rc = check_workspace(kChunk, a, w.total)) return rc;
-
+// The kernel parameters of a validated chunk call with S splits and its workspace laid out as w
+static ChunkKernelParams chunk_params(const sfa_decode_args *a, const DecodeCall &dc, int num_tokens, int S,
+                                      const DecodeWorkspace &w) {
     ChunkKernelParams p;
     memset(&p, 0, sizeof(p));
     p.d = decode_params(a, dc.hkv, dc.page_shift, S, dc.stride);
@@ -486,8 +481,58 @@ int sfa_decode_chunk(const sfa_decode_args *a, int num_tokens, int64_t qkv_token
     p.tok_stride = dc.tok;
     p.n = num_tokens;
     p.G = dc.group;
-    p.R = rows;
-    return launch_decode_chunk(p, a->dtype, a->head_dim, (hipStream_t)stream);
+    p.R = num_tokens * dc.group;
+    return p;
+}
+
+int sfa_decode_chunk(const sfa_decode_args *a, int num_tokens, int64_t qkv_token_stride, void *stream) {
+    DecodeCall dc;
+    if (const int rc = validate_decode_call(kChunk, a, num_tokens, qkv_token_stride, &dc)) return rc;
+    if (a->batch_size == 0 || num_tokens == 0) return SFA_OK;
+
+    const int rows = num_tokens * dc.group;
+    const int S = a->num_splits > 0 ? a->num_splits : chunk_auto_splits(a->batch_size, dc.hkv, rows, a->memory_max_len);
+    const DecodeWorkspace w = chunk_workspace(a->batch_size, dc.hkv, rows, S, a->head_dim);
+    if (const int rc = check_workspace(kChunk, a, w.total)) return rc;
+    return launch_decode_chunk(chunk_params(a, dc, num_tokens, S, w), a->dtype, a->head_dim, (hipStream_t)stream);
+}
+
+// The sliding-window twins of the chunk and varlen calls.  When the library picks the split count it is the twin's rule
+// over the rows a sequence can read instead of memory_max_len: min(memory_max_len, window - 1 + count), count = the
+// call's num_tokens / total_tokens (the first token reads window rows, the last one ends count - 1 rows later).  The
+// rule never grows with that argument, so a workspace sized for the call without a window is never too small.
+static int window_rows(int M, int window, int count) {
+    const long long r = (long long)(window > 1 ? window : 1) - 1 + count;
+    return (int)(r < M ? (r > 1 ? r : 1) : M);
+}
+
+size_t sfa_decode_chunk_window_workspace_bytes(int batch_size, int num_heads, int num_heads_kv, int head_dim,
+                                               int memory_max_len, int num_tokens, int window, int num_splits) {
+    return sfa_decode_chunk_workspace_bytes(batch_size, num_heads, num_heads_kv, head_dim,
+                                            window_rows(memory_max_len, window, num_tokens), num_tokens, num_splits);
+}
+
+int sfa_decode_chunk_window(const sfa_decode_args *a, int num_tokens, int64_t qkv_token_stride, int window,
+                            void *stream) {
+    DecodeCall dc;
+    if (const int rc = validate_decode_call(kChunkWindow, a, num_tokens, qkv_token_stride, &dc)) return rc;
+    if (window < 1) return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk_window: window=%d must be >= 1", window);
+    if (a->batch_size == 0 || num_tokens == 0) return SFA_OK;
+
+    const int rows = num_tokens * dc.group;
+    int S = a->num_splits > 0 ? a->num_splits
+                              : chunk_auto_splits(a->batch_size, dc.hkv, rows, window_rows(a->memory_max_len, window, num_tokens));
+    // as in sfa_decode: a workspace sized for fewer splits than the library would pick gets the largest count it holds
+    if (a->num_splits <= 0 && a->workspace)
+        while (S > 1 && a->workspace_bytes < chunk_workspace(a->batch_size, dc.hkv, rows, S, a->head_dim).total) --S;
+    const DecodeWorkspace w = chunk_workspace(a->batch_size, dc.hkv, rows, S, a->head_dim);
+    if (const int rc = check_workspace(kChunkWindow, a, w.total)) return rc;
+
+    ChunkWindowKernelParams p;
+    memset(&p, 0, sizeof(p));
+    p.base = chunk_params(a, dc, num_tokens, S, w);
+    p.window = window;
+    return launch_decode_chunk_window(p, a->dtype, a->head_dim, (hipStream_t)stream);
 }
 
 // (rows = total_tokens * group packed query rows per kv head)
@@ -505,27 +550,34 @@ size_t sfa_decode_varlen_workspace_bytes(int batch_size, int num_heads, int num_
     return varlen_workspace(batch_size, hkv, rows, S, head_dim).total;
 }
 
-int sfa_decode_varlen(const sfa_decode_args *a, const void *cu_tokens, int total_tokens, int64_t qkv_token_stride,
-                      void *stream) {
+// sfa_decode_varlen and its sliding-window twin (windowed) up to the launch: the checks, the split count, the
+// workspace and the kernel parameters
+static int varlen_call(const EntryPoint &e, const sfa_decode_args *a, const void *cu_tokens, int total_tokens,
+                       int64_t qkv_token_stride, bool windowed, int window, VarlenKernelParams *out) {
     DecodeCall dc;
-    if (a && !cu_tokens) return fail(SFA_ERR_NULL_POINTER, "sfa_decode_varlen: cu_tokens is NULL");
-    if (const int rc = validate_decode_call(kVarlen, a, total_tokens, qkv_token_stride, &dc)) return rc;
-    if ((uintptr_t)cu_tokens & 3) return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_varlen: cu_tokens must be 4-byte aligned");
+    if (a && !cu_tokens) return fail(SFA_ERR_NULL_POINTER, "%s: cu_tokens is NULL", e.fn);
+    if (const int rc = validate_decode_call(e, a, total_tokens, qkv_token_stride, &dc)) return rc;
+    if ((uintptr_t)cu_tokens & 3) return fail(SFA_ERR_BAD_SHAPE, "%s: cu_tokens must be 4-byte aligned", e.fn);
+    if (windowed && window < 1) return fail(SFA_ERR_BAD_SHAPE, "%s: window=%d must be >= 1", e.fn, window);
     const long long rows = (long long)total_tokens * dc.group;
     if (a->batch_size == 0 || total_tokens == 0) return SFA_OK;
 
     const int hkv = dc.hkv, bound = varlen_plan_bound(a->batch_size, rows);
-    const int S = a->num_splits > 0 ? a->num_splits : varlen_auto_splits(a->batch_size, hkv, rows, a->memory_max_len);
+    const int M = windowed ? window_rows(a->memory_max_len, window, total_tokens) : a->memory_max_len;
+    int S = a->num_splits > 0 ? a->num_splits : varlen_auto_splits(a->batch_size, hkv, rows, M);
+    // (window) as in sfa_decode: a workspace sized for fewer splits than the library would pick gets the largest count it
+    // holds
+    if (windowed && a->num_splits <= 0 && a->workspace)
+        while (S > 1 && a->workspace_bytes < varlen_workspace(a->batch_size, hkv, rows, S, a->head_dim).total) --S;
     // the attention kernel's 1-D grid: one workgroup per (plan slot, kv head, split)
     if ((long long)bound * hkv * S > INT_MAX)
         return fail(SFA_ERR_BAD_SHAPE,
-                    "sfa_decode_varlen: total_tokens=%d, batch_size=%d, num_heads_kv=%d and num_splits=%d need more than "
-                    "2^31 - 1 attention workgroups", total_tokens, a->batch_size, hkv, S);
+                    "%s: total_tokens=%d, batch_size=%d, num_heads_kv=%d and num_splits=%d need more than "
+                    "2^31 - 1 attention workgroups", e.fn, total_tokens, a->batch_size, hkv, S);
     const DecodeWorkspace w = varlen_workspace(a->batch_size, hkv, rows, S, a->head_dim);
-    if (const int rc = check_workspace(kVarlen, a, w.total)) return rc;
+    if (const int rc = check_workspace(e, a, w.total)) return rc;
 
-    VarlenKernelParams p;
-    memset(&p, 0, sizeof(p));
+    VarlenKernelParams &p = *out;
     p.c.d = decode_params(a, hkv, dc.page_shift, S, 0);
     p.c.tok_stride = dc.tok;
     p.c.G = dc.group;
@@ -538,7 +590,33 @@ int sfa_decode_varlen(const sfa_decode_args *a, const void *cu_tokens, int total
     p.c.q_rot = (uint16_t *)(ws + w.q_rot);
     p.c.d.part_o = (float *)(ws + w.part_o);
     p.c.d.part_ml = (float2 *)(ws + w.part_ml);
+    return SFA_OK;
+}
+
+int sfa_decode_varlen(const sfa_decode_args *a, const void *cu_tokens, int total_tokens, int64_t qkv_token_stride,
+                      void *stream) {
+    VarlenKernelParams p;
+    memset(&p, 0, sizeof(p));
+    if (const int rc = varlen_call(kVarlen, a, cu_tokens, total_tokens, qkv_token_stride, false, 0, &p)) return rc;
+    if (!p.cu_tokens) return SFA_OK;            // nothing to do
     return launch_decode_varlen(p, a->dtype, a->head_dim, (hipStream_t)stream);
+}
+
+size_t sfa_decode_varlen_window_workspace_bytes(int batch_size, int num_heads, int num_heads_kv, int head_dim,
+                                                int memory_max_len, int total_tokens, int window, int num_splits) {
+    return sfa_decode_varlen_workspace_bytes(batch_size, num_heads, num_heads_kv, head_dim,
+                                             window_rows(memory_max_len, window, total_tokens), total_tokens, num_splits);
+}
+
+int sfa_decode_varlen_window(const sfa_decode_args *a, const void *cu_tokens, int total_tokens, int64_t qkv_token_stride,
+                             int window, void *stream) {
+    VarlenWindowKernelParams p;
+    memset(&p, 0, sizeof(p));
+    if (const int rc = varlen_call(kVarlenWindow, a, cu_tokens, total_tokens, qkv_token_stride, true, window, &p.base))
+        return rc;
+    if (!p.base.cu_tokens) return SFA_OK;       // nothing to do
+    p.window = window;
+    return launch_decode_varlen_window(p, a->dtype, a->head_dim, (hipStream_t)stream);
 }
 
 int sfa_prefill_fwd(const sfa_prefill_args *a, void *stream) {

@@ -16,6 +16,10 @@
 //
 // With the uniform policy every one of these is the expression the chunk kernels used to spell out, and the kernels
 // compile to the code they compiled to before the split (DESIGN.md lists the resource usage of both).
+//
+// A sliding window (sfa_decode_chunk_window / sfa_decode_varlen_window) is a compile-time property of the geometry:
+// WindowGeo<BASE, P> below is BASE with `static constexpr bool kWindow = true` and window(gp).  Only chunk_attn_kernel
+// looks at it; without the flag none of the window's code is compiled.
 #pragma once
 #include "decode_chunk_common.h"
 #include "prefill_core.h"
@@ -28,6 +32,44 @@ using decode::pack8;
 using decode::unpack8;
 
 constexpr uint16_t nan_bits(int dtype_id) { return dtype_id == 0 ? 0x7e00 : 0x7fc0; }
+
+// Does GEO carry a sliding window?
+template <class GEO, class = void> struct geo_window : std::false_type {};
+template <class GEO> struct geo_window<GEO, std::void_t<decltype(GEO::kWindow)>> : std::bool_constant<GEO::kWindow> {};
+
+// BASE with a window: P holds BASE's Params as `base` and the window (>= 1) as `window`
+template <class BASE, class P>
+struct WindowGeo {
+    using Params = P;
+    static constexpr bool kWindow = true;
+    static __device__ __forceinline__ int window(const P &gp) { return gp.window; }
+    static __device__ __forceinline__ const ChunkKernelParams &chunk(const P &gp) { return BASE::chunk(gp.base); }
+    static __device__ __forceinline__ bool prologue(const P &gp, int &b, int &t, int &n) {
+        return BASE::prologue(gp.base, b, t, n);
+    }
+    static __device__ __forceinline__ long long qkv_off(const P &gp, int b, int t) { return BASE::qkv_off(gp.base, b, t); }
+    static __device__ __forceinline__ bool attn(const P &gp, int &b, int &qt, int &hs, int &n, int &R) {
+        return BASE::attn(gp.base, b, qt, hs, n, R);
+    }
+    static __device__ __forceinline__ long long q_row(const P &gp, int b, int hk, long long r) {
+        return BASE::q_row(gp.base, b, hk, r);
+    }
+    static __device__ __forceinline__ long long part_row(const P &gp, int b, int hk, int split, long long r) {
+        return BASE::part_row(gp.base, b, hk, split, r);
+    }
+    static __device__ __forceinline__ long long o_tok(const P &gp, int b, int t) { return BASE::o_tok(gp.base, b, t); }
+    static __device__ __forceinline__ bool combine(const P &gp, long long row, long long &grp, long long &rows,
+                                                   long long &r, long long &tok, int &head) {
+        return BASE::combine(gp.base, row, grp, rows, r, tok, head);
+    }
+};
+
+// The window's lower mask of a half-tile of fresh scores (mask_half's register layout): keys below lo get -inf
+__device__ __forceinline__ void mask_low(f32x16 &s, int kbase, int h2, int lo) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+        if (kbase + (r & 3) + 8 * (r >> 2) + 4 * h2 < lo) s[r] = ninf();
+}
 
 template <class GEO, class Tr, int D, bool PAGED>
 __global__ void __launch_bounds__(256)
@@ -141,20 +183,45 @@ chunk_attn_kernel(const typename GEO::Params gp) {
     }
 
     // ---- the key range of this workgroup: tiles [ts0, wg_end) of the Kb = pos + n keys ----
+    // WIN: the row with causal limit `lim` sees the keys [max(0, lim + 1 - window), lim].  No key below lo0, the lower
+    // bound of the sequence's first token, is visible to any row, so the splits share the tiles [tlo, ntot) and a
+    // workgroup starts at the tile of its q-tile's first row's lower bound, if that is later than its split's.
+    constexpr bool WIN = geo_window<GEO>::value;
+    int win = 0;
+    if constexpr (WIN) win = GEO::window(gp);
+    auto low_of = [&](int limit) -> int { return max(0, limit + 1 - win); };    // (WIN only)
     const int Kb = pos + ntok;
     const int ntot = (Kb + kBN - 1) / kBN;
-    const int per = (ntot + S - 1) / S;         // tiles per split
-    const int ts0 = split * per;
+    const int lo0 = WIN ? low_of(pos) : 0;
+    const int tlo = lo0 / kBN;
+    const int per = (ntot - tlo + S - 1) / S;   // tiles per split
+    const int ts0s = tlo + split * per;         // the split's first tile
+    const int ts0 = WIN ? max(ts0s, low_of(pos + q0 / G) / kBN) : ts0s;
     const int rlast = min(q0 + kBM, R) - 1;     // last query row of the q-tile
-    const int wg_end = min(min(ntot, ts0 + per), (pos + rlast / G) / kBN + 1);
+    const int wg_end = min(min(ntot, ts0s + per), (pos + rlast / G) / kBN + 1);
     const int nt = max(0, wg_end - ts0);        // tiles the workgroup stages (workgroup-uniform)
     int ntw = 0;                                // tiles this wave computes on (wave-uniform)
     if (wq0 < R) ntw = max(0, min(wg_end, (pos + min(wq0 + 31, R - 1) / G) / kBN + 1) - ts0);
     int lim[NQB];                               // last visible key of this lane's row
     lim[0] = pos + min(qrow, R - 1) / G;
     const int wlim = pos + min(wq0, R - 1) / G; // the smallest limit of the wave's rows
+    // WIN: this lane's lower bound, the largest one of the wave's rows, and the leading tiles of the workgroup that lie
+    // wholly below the smallest one: the wave only stages during those (the mirror of the idle steps at the end)
+    const int lo_r = WIN ? low_of(lim[0]) : 0;
+    const int wlo = WIN ? low_of(pos + min(wq0 + 31, R - 1) / G) : 0;
+    const int tw0 = WIN ? min(max(0, low_of(wlim) / kBN - ts0), ntw) : 0;
     // bit 0 set: the 32 keys starting at KBASE need masking for this wave's rows (lim <= Kb - 1 always)
-    auto mask_bits = [&](int kbase) -> int { return kbase + 31 > wlim ? 1 : 0; };
+    auto mask_bits = [&](int kbase) -> int { return (kbase + 31 > wlim || (WIN && kbase < wlo)) ? 1 : 0; };
+    // WIN: the lower mask, applied by h_block next to the causal one on the halves mask_bits flags
+    auto low_mask = [&] {
+        if constexpr (WIN) {
+            return [&](f32x16 &s, int kbase, int) {
+                if (kbase < wlo) mask_low(s, kbase, h2, lo_r);
+            };
+        } else {
+            return NoLowMask();
+        }
+    }();
 
     // ---- staging: thread owns chunks (row st_row + i*ROWSTEP, chunk st_ch), i < NLD, of every tile ----
     const int st_row = tid / CPR, st_ch = tid % CPR;
@@ -173,6 +240,10 @@ chunk_attn_kernel(const typename GEO::Params gp) {
     const int rmask = (1 << psh) - 1;
     const int ragged_tile = (Kb % kBN) ? ntot - 1 : -1;
     const int last0 = Kb - 1 - (ntot - 1) * kBN;            // last valid row of the last tile
+    // WIN: the first tile (tlo) is clamped from below as well, to max(row, lo0): nothing below lo0 is read, in the
+    // cache or in the table -- a masked key has weight 0, but 0 * NaN is NaN in P.V.  Its offsets are worked out per
+    // tile from the clamped row rather than kept in a third and fourth set of registers.
+    const int first0 = lo0 - tlo * kBN;                     // first valid row of the first tile
     const int row0_ = st_row, row1_ = st_row + ROWSTEP;
     const int rr0_ = min(row0_, last0), rr1_ = min(row1_, last0);
     // (32 bit: 64 rows * rsb < 2^31, checked by sfa_decode_chunk)
@@ -193,7 +264,7 @@ chunk_attn_kernel(const typename GEO::Params gp) {
         for (int j = 0; j < NPS; ++j) {
             o[j] = 0;
             if ((j << psh) < kBN) {
-                const int r = min(r0 + (j << psh), Kb - 1);
+                const int r = min(WIN ? max(r0 + (j << psh), lo0) : r0 + (j << psh), Kb - 1);
                 int pg = tbl[r >> p.page_shift];
                 if ((unsigned)pg >= (unsigned)p.num_pages) {    // a READ page outside the pool: not dereferenced
                     bad_page = 1;
@@ -208,7 +279,7 @@ chunk_attn_kernel(const typename GEO::Params gp) {
         return s == 0 ? o[0] : s == 1 ? o[1] : s == 2 ? o[2] : o[3];
     };
     constexpr int NOPS = 2 * NLD;   // op n: even = K chunk n/2, odd = V chunk n/2
-    struct TileSrc { long long k[NPS], v[NPS]; bool rk, rv; };
+    struct TileSrc { long long k[NPS], v[NPS]; bool rk, rv; int fk, fv; };      // fk / fv: WIN, first valid row
     auto tile_of = [&](int t) -> int { return min(ts0 + t, wg_end - 1); };  // past the end: re-read the last tile
     auto tile_src = [&](int pos_k, int pos_v) -> TileSrc {
         const int tk = tile_of(pos_k), tv = tile_of(pos_v);
@@ -217,14 +288,24 @@ chunk_attn_kernel(const typename GEO::Params gp) {
         tile_base(tv, ts.v);
         ts.rk = tk == ragged_tile;
         ts.rv = tv == ragged_tile;
+        if constexpr (WIN) {
+            ts.fk = tk == tlo ? first0 : 0;
+            ts.fv = tv == tlo ? first0 : 0;
+        }
         return ts;
     };
+    auto win_off = [&](const long long (&o)[NPS], int i, int first, bool ragged) -> long long {
+        const int r = min(max(i == 0 ? row0_ : row1_, first), ragged ? last0 : kBN - 1);
+        return sel(o, r >> psh) + lane_off(r);
+    };
     auto ld_k = [&](const TileSrc &ts, int i) -> uint4 {
+        if constexpr (WIN) return *reinterpret_cast<const uint4 *>(kg + win_off(ts.k, i, ts.fk, ts.rk));
         const long long off = i == 0 ? (ts.rk ? sel(ts.k, sr0) + or0 : sel(ts.k, sw0) + ow0)
                                      : (ts.rk ? sel(ts.k, sr1) + or1 : sel(ts.k, sw1) + ow1);
         return *reinterpret_cast<const uint4 *>(kg + off);
     };
     auto ld_v = [&](const TileSrc &ts, int i) -> uint4 {
+        if constexpr (WIN) return *reinterpret_cast<const uint4 *>(vg + win_off(ts.v, i, ts.fv, ts.rv));
         const long long off = i == 0 ? (ts.rv ? sel(ts.v, sr0) + or0 : sel(ts.v, sw0) + ow0)
                                      : (ts.rv ? sel(ts.v, sr1) + or1 : sel(ts.v, sw1) + ow1);
         return *reinterpret_cast<const uint4 *>(vg + off);
@@ -316,7 +397,13 @@ chunk_attn_kernel(const typename GEO::Params gp) {
         Vec kpre[PF];
 #pragma unroll
         for (int i = 0; i < PF; ++i) kpre[i] = bitcast<Vec>(make_uint4(0, 0, 0, 0));
-        if (ntw > 0) {
+        if constexpr (WIN) {                    // leading idle steps: tiles below every row of this wave
+            for (; t < tw0; ++t) {
+                SFA_STAGE_AND_SYNC(t);
+                SFA_ADVANCE();
+            }
+        }
+        if (WIN ? t < ntw : ntw > 0) {
 #pragma unroll
             for (int ks = 0; ks < NKS; ++ks) {
                 const Vec a = bitcast<Vec>(*reinterpret_cast<const uint4 *>(k_rd + kcur + 32 * ks));
@@ -339,7 +426,7 @@ chunk_attn_kernel(const typename GEO::Params gp) {
                 for (int n = j * NOPS / NPV_; n < (j + 1) * NOPS / NPV_; ++n) store_op(n, k2, v1);
             };
             h_block<Tr, D, NQB, PF, ORD, 1, 0, true, true>(kb, vb, kb1, qf, sB, sA, acc, c2, mxA, mxB,
-                                                           mask_bits(kbase), kbase, h2, lim, kpre, NoHook(), st_hook);
+                                                           mask_bits(kbase), kbase, h2, lim, kpre, NoHook(), st_hook, low_mask);
             __syncthreads();
             const TileSrc ts = tile_src(t + 3, t + 2);
             auto ld_hook = [&](int i) {
@@ -347,7 +434,7 @@ chunk_attn_kernel(const typename GEO::Params gp) {
                 for (int n = (i - 1) * NOPS / (NKS - 1); n < i * NOPS / (NKS - 1); ++n) load_op(n, ts);
             };
             h_block<Tr, D, NQB, PF, ORD, 0, 1, true, true>(kb1, vb, kb1, qf, sA, sB, acc, c2, mxB, mxA,
-                                                           mask_bits(kbase + 32), kbase + 32, h2, lim, kpre, ld_hook);
+                                                           mask_bits(kbase + 32), kbase + 32, h2, lim, kpre, ld_hook, NoHook(), low_mask);
             SFA_ADVANCE();
         }
         // ---- TAIL step: this wave's last tile ----
@@ -355,10 +442,11 @@ chunk_attn_kernel(const typename GEO::Params gp) {
             const char *kb = k_rd + kcur, *vb = v_rd + vcur;
             const int kbase = (ts0 + t) * kBN;
             h_block<Tr, D, NQB, PF, ORD, 1, 0, true, false>(kb, vb, kb, qf, sB, sA, acc, c2, mxA, mxB,
-                                                            mask_bits(kbase), kbase, h2, lim, kpre);
+                                                            mask_bits(kbase), kbase, h2, lim, kpre, NoHook(), NoHook(), low_mask);
             SFA_STAGE_AND_SYNC(t);
             h_block<Tr, D, NQB, PF, ORD, 0, 1, false, false>(kb, vb, kb, qf, sA, sB, acc, c2, mxB, mxA,
-                                                             mask_bits(kbase + 32), kbase + 32, h2, lim, kpre);
+                                                             mask_bits(kbase + 32), kbase + 32, h2, lim, kpre, NoHook(), NoHook(),
+                                                             low_mask);
             SFA_ADVANCE();
             ++t;
         }
@@ -380,7 +468,7 @@ chunk_attn_kernel(const typename GEO::Params gp) {
     }
     if (qrow < R) {
         if (S == 1) {
-            // every row sees key 0 (pos >= 0), so ltot > 0 -- or NaN after a bad page
+            // every row sees key 0 (pos >= 0; WIN: its own key), so ltot > 0 -- or NaN after a bad page
             store_o_row<Tr, D>(out_row(qrow), acc.o[0], 1.0f / ltot, h2);
         } else {
             // un-normalised O^T: lane (l31, h2) holds columns 32d + 8g + 4*h2 + {0..3} in registers 4g..4g+3

@@ -16,57 +16,19 @@
 //      key range [0, Kb) is split (on the device, in whole 64-key tiles) and each split writes fp32 partials.
 //   3. chunk_combine_kernel (num_splits > 1 only): merges the partials, as decode_combine_kernel does.  A split
 //      that lies past a row's causal limit left (m = -inf, l = 0) for it, which the merge ignores.
-// The kernels themselves are in decode_chunk_body.h, shared with the ragged sfa_decode_varlen; this file holds the
-// uniform geometry (UniformGeo) and its grids.
+// The kernels themselves are in decode_chunk_body.h, shared with the ragged sfa_decode_varlen; decode_chunk_geo.h holds
+// the uniform geometry (UniformGeo), this file its grids.
 // Rejection (decode_chunk_common.h, reject_code): every kernel re-derives it from seq_len / block_table; the
 // prologue raises the sticky status bit and touches no cache row, the attention kernel writes NaN outputs.
 // A block_table entry outside the pool on a page that is only READ is replaced by page 0, raises bit 2 and turns
 // the workgroup's outputs into NaN.
-#include "decode_chunk_body.h"
+#include "decode_chunk_geo.h"
 
 namespace sfa {
 
 namespace {
 
 using namespace prefill;
-
-// The same n for every sequence: dense [B, n, ...] qkv / o, the rotated Q [B, Hkv, R, D], partials [B, Hkv, S, R, ..],
-// one attention workgroup per (q-tile, kv head * S + split, batch).
-struct UniformGeo {
-    using Params = ChunkKernelParams;
-    static __device__ __forceinline__ const ChunkKernelParams &chunk(const Params &cp) { return cp; }
-    static __device__ __forceinline__ bool prologue(const Params &cp, int &b, int &t, int &n) {
-        t = blockIdx.x, b = blockIdx.y, n = cp.n;
-        return true;
-    }
-    static __device__ __forceinline__ long long qkv_off(const Params &cp, int b, int t) {
-        return (long long)b * cp.d.qkv_stride + (long long)t * cp.tok_stride;
-    }
-    static __device__ __forceinline__ bool attn(const Params &cp, int &b, int &qt, int &hs, int &n, int &R) {
-        qt = (int)gridDim.x - 1 - (int)blockIdx.x;
-        hs = blockIdx.y;
-        b = blockIdx.z, n = cp.n, R = cp.R;
-        return true;
-    }
-    static __device__ __forceinline__ long long q_row(const Params &cp, int b, int hk, long long r) {
-        return ((long long)b * cp.d.Hkv + hk) * cp.R + r;
-    }
-    static __device__ __forceinline__ long long part_row(const Params &cp, int b, int hk, int split, long long r) {
-        return (((long long)b * cp.d.Hkv + hk) * cp.d.num_splits + split) * cp.R + r;
-    }
-    static __device__ __forceinline__ long long o_tok(const Params &cp, int b, int t) { return (long long)b * cp.n + t; }
-    static __device__ __forceinline__ bool combine(const Params &cp, long long row, long long &grp, long long &rows,
-                                                   long long &r, long long &tok, int &head) {
-        if (row >= (long long)cp.d.B * cp.d.Hkv * cp.R) return false;
-        const int ri = (int)(row % cp.R);
-        grp = row / cp.R;                       // b * Hkv + hk
-        const int hk = (int)(grp % cp.d.Hkv), b = (int)(grp / cp.d.Hkv);
-        rows = cp.R, r = ri;
-        tok = (long long)b * cp.n + ri / cp.G;
-        head = hk * cp.G + ri % cp.G;
-        return true;
-    }
-};
 
 }  // namespace
 

@@ -100,15 +100,20 @@ __device__ __forceinline__ void finish_prescaled(f32x16 &s, Acc<D, NQB> &acc, in
 //   mxN[q]    out: this lane's max over the 16 new scores
 //   mask_o    bit q set: sO[q] holds keys that must be masked (diagonal / ragged tiles)
 //   PF        how many slots ahead of its MFMAs a fragment is read
+//   low_mask  low_mask(sO[q], kbase_o, q) runs right after mask_half on a half that mask_o flags, before the row max
+//             is taken again: a caller with a lower key bound as well (the sliding window of decode_chunk_body.h) puts
+//             it there.  Exact-scale mode only; the default does nothing.
 struct NoHook { __device__ __forceinline__ void operator()(int) const {} };
+struct NoLowMask { __device__ __forceinline__ void operator()(f32x16 &, int, int) const {} };
 
-template <class Tr, int D, int NQB, int PF, int ORD, int HN, int HO, bool DO_QK, bool PREF, class QkHook = NoHook, class PvHook = NoHook, int PH = 1 - HN>
+template <class Tr, int D, int NQB, int PF, int ORD, int HN, int HO, bool DO_QK, bool PREF, class QkHook = NoHook, class PvHook = NoHook, int PH = 1 - HN, class LowMask = NoLowMask>
 __device__ __forceinline__ void h_block(const char *kb, const char *vb, const char *kb_pref,
                                         const typename Tr::mfma_vec (&qf)[NQB][D / 16],
                                         f32x16 (&sN)[NQB], f32x16 (&sO)[NQB], Acc<D, NQB> &acc, float c2,
                                         const float (&mxO)[NQB], float (&mxN)[NQB], int mask_o, int kbase_o,
                                         int h2, const int (&lim)[NQB], typename Tr::mfma_vec (&kpre)[PF],
-                                        const QkHook &qk_hook = QkHook(), const PvHook &pv_hook = PvHook()) {
+                                        const QkHook &qk_hook = QkHook(), const PvHook &pv_hook = PvHook(),
+                                        const LowMask &low_mask = LowMask()) {
     // qk_hook(i) / pv_hook(j): extra work the caller wants issued inside QK slot i / PV slot j
     // (staging loads and stores spread under the MFMAs instead of bunched at the barrier)
     using Vec = typename Tr::mfma_vec;
@@ -167,6 +172,7 @@ __device__ __forceinline__ void h_block(const char *kb, const char *vb, const ch
         float mxl = mxO[q];
         if (mask_o & (1 << q)) {                        // wave-uniform, diagonal / ragged tiles only
             mask_half(sO[q], kbase_o, h2, lim[q]);
+            low_mask(sO[q], kbase_o, q);
             mxl = lane_rowmax(sO[q]);
         }
         // (a row's two lanes share msc, so the trigger needs no cross-lane exchange)

@@ -72,6 +72,18 @@ struct VarlenKernelParams {
     int bound;              // plan entries = grid.x of the attention kernel
 };
 
+// sfa_decode_chunk_window / sfa_decode_varlen_window (decode_chunk_window_kernel.hip, decode_varlen_window_kernel.hip):
+// the two calls above with a sliding window.  The window rides behind the unchanged parameters, so the kernels without
+// one keep their argument layout.
+struct ChunkWindowKernelParams {
+    ChunkKernelParams base;
+    int window;             // >= 1: token t at pos + t attends to the rows max(0, pos + t + 1 - window) .. pos + t
+};
+struct VarlenWindowKernelParams {
+    VarlenKernelParams base;
+    int window;
+};
+
 // sfa_decode_kv8 (decode_kv8_kernel.hip): caches of one byte per element (e4m3) with a scale per kv head.
 struct Kv8KernelParams {
     DecodeKernelParams d;   // every field keeps its sfa_decode meaning; d.k_cache / d.v_cache point to bytes, the cache
@@ -110,6 +122,8 @@ int launch_decode_gqa_mfma(const DecodeKernelParams &p, int dtype, int head_dim,
 int launch_decode_combine(const DecodeKernelParams &p, int dtype, int head_dim, hipStream_t stream);
 int launch_decode_chunk(const ChunkKernelParams &p, int dtype, int head_dim, hipStream_t stream);
 int launch_decode_varlen(const VarlenKernelParams &p, int dtype, int head_dim, hipStream_t stream);
+int launch_decode_chunk_window(const ChunkWindowKernelParams &p, int dtype, int head_dim, hipStream_t stream);
+int launch_decode_varlen_window(const VarlenWindowKernelParams &p, int dtype, int head_dim, hipStream_t stream);
 // decode_kv8_kernel.hip: the attention kernel over e4m3 caches plus the split combine; the 16-bit -> e4m3 row copy
 int launch_decode_kv8(const Kv8KernelParams &p, int dtype, int head_dim, hipStream_t stream);
 int launch_kv8_quantize(void *dst, const void *src, const float *scale, long long rows, int Hkv, int head_dim,

@@ -15,6 +15,8 @@ libStarFlashAttention.so.  The public operators:
                       16-bit cache rows into such a cache (new entry points).
   flash_decode_window(...)  flash_decode with a sliding window: the token attends to the last `window` positions only
                       (new entry point).
+  flash_decode_chunk_window(...) / flash_decode_varlen_window(...)  flash_decode_chunk / flash_decode_varlen with that
+                      window: what n successive flash_decode_window calls give (new entry points).
 """
 import ctypes
 import math
@@ -327,6 +329,66 @@ def flash_decode_varlen(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_tabl
         ws = _workspace(dev, lib.sfa_decode_varlen_workspace_bytes(B, H, Hkv, D, M, T, S))
         cu = ctypes.c_void_p(cu_tokens.data_ptr())
         _call_decode(dev, a, 0, S, ws, lambda args, stream: lib.sfa_decode_varlen(args, cu, T, 0, stream))
+    return o
+
+
+def _window_int(window):
+    W = int(window)
+    _require(-2 ** 31 <= W < 2 ** 31, f"window={window} does not fit an int")
+    return W
+
+
+def flash_decode_chunk_window(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o,
+                              batch_size, memory_max_len, num_heads, head_dim, rotary_embedding_dim,
+                              max_input_length, num_layer, idx_layer, window, *, num_splits=0,
+                              rotary_cos_table=None, rotary_sin_table=None, softmax_scale=None, kv_layout="blmhd",
+                              block_table=None, num_heads_kv=None):
+    """flash_decode_chunk with a sliding window (include/star_flash_attn.h, sfa_decode_chunk_window): the result of n
+    successive flash_decode_window calls.  Token t of sequence b, at position seq_len[b] + t, attends to the rows
+    [max(0, seq_len[b] + t + 1 - window), seq_len[b] + t].  window >= 1; every other argument as in flash_decode_chunk.
+    Cache rows below lo_0 = max(0, seq_len[b] + 1 - window), and block_table entries of pages wholly below lo_0, are
+    never read.  Returns `o`."""
+    lib = _lib.load()
+    _require(isinstance(qkv, torch.Tensor) and qkv.dim() in (4, 5),
+             f"qkv must be [B, n, 3, H, D] or [B, n, H + 2*Hkv, D] (got {tuple(getattr(qkv, 'shape', ()))})")
+    n = int(qkv.shape[1])
+    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
+                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
+                                      kv_layout, block_table, num_heads_kv, tokens=n)
+    W = _window_int(window)
+    dev = qkv.device
+    with torch.cuda.device(dev):
+        S = int(num_splits) if num_splits and num_splits > 0 else 0
+        ws = _workspace(dev, lib.sfa_decode_chunk_window_workspace_bytes(B, H, Hkv, D, M, n, W, S))
+        _call_decode(dev, a, 0, S, ws, lambda args, stream: lib.sfa_decode_chunk_window(args, n, 0, W, stream))
+    return o
+
+
+def flash_decode_varlen_window(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, cu_tokens,
+                               batch_size, memory_max_len, num_heads, head_dim, rotary_embedding_dim,
+                               max_input_length, num_layer, idx_layer, window, *, num_splits=0,
+                               rotary_cos_table=None, rotary_sin_table=None, softmax_scale=None, kv_layout="blmhd",
+                               block_table=None, num_heads_kv=None):
+    """flash_decode_varlen with a sliding window (include/star_flash_attn.h, sfa_decode_varlen_window): every packed
+    token gets what flash_decode_chunk_window gives it at pos = seq_len[b].  window >= 1; every other argument as in
+    flash_decode_varlen.  Returns `o`."""
+    lib = _lib.load()
+    _require(isinstance(qkv, torch.Tensor) and qkv.dim() in (3, 4),
+             f"qkv must be [T, 3, H, D] or [T, H + 2*Hkv, D] (got {tuple(getattr(qkv, 'shape', ()))})")
+    T = int(qkv.shape[0])
+    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
+                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
+                                      kv_layout, block_table, num_heads_kv, packed=T)
+    W = _window_int(window)
+    dev = qkv.device
+    _check_gpu_tensor(cu_tokens, "cu_tokens", torch.int32, (B + 1,), dev)
+    with torch.cuda.device(dev):
+        S = int(num_splits) if num_splits and num_splits > 0 else 0
+        ws = _workspace(dev, lib.sfa_decode_varlen_window_workspace_bytes(B, H, Hkv, D, M, T, W, S))
+        cu = ctypes.c_void_p(cu_tokens.data_ptr())
+        _call_decode(dev, a, 0, S, ws, lambda args, stream: lib.sfa_decode_varlen_window(args, cu, T, 0, W, stream))
     return o
 
 
