@@ -24,6 +24,7 @@
  *   sfa_kv8_quantize            <- (no reference function: 16-bit cache rows -> fp8 cache rows)
  *   sfa_decode_window           <- (no reference function: sfa_decode over the last `window` positions)
  *   sfa_decode_chunk_window     <- (no reference function: sfa_decode_chunk / sfa_decode_varlen with that window)
+ *   sfa_decode_kv8_window       <- (no reference function: sfa_decode_kv8 over the last `window` positions)
  * The Python-facing mha_fwd_cuda (src/flash_api.cpp:42-68) and the C++ template
  * surface (src/flash_attn.h) in this repo are thin layers over these symbols.
  */
@@ -49,7 +50,8 @@ extern "C" {
  *      sfa_decode_window and sfa_decode_window_workspace_bytes (sliding-window decode) added under the same version,
  *      beside an unchanged sfa_decode_args: callers detect them by symbol
  *      sfa_decode_chunk_window, sfa_decode_varlen_window and their _workspace_bytes functions (the sliding window in the
- *      multi-token calls) added under the same version, in the same way */
+ *      multi-token calls) added under the same version, in the same way
+ *      sfa_decode_kv8_window (the sliding window over an fp8 KV cache) added under the same version, in the same way */
 #define SFA_ABI_VERSION 4
 
 typedef enum sfa_status {
@@ -338,7 +340,8 @@ size_t sfa_decode_window_workspace_bytes(int batch_size, int num_heads, int num_
  * sfa_decode_chunk_workspace_bytes / sfa_decode_varlen_workspace_bytes is never too small; one that holds fewer splits
  * than the library would pick gets the largest count it holds.  The split key range is the tiles that hold
  * [lo_0, pos + n), not [0, pos + n): a short window over a long history is shared by all splits.
- * Not served: an fp8 cache, head_dim 256, ring-buffer caches, attention sinks, soft-capping.
+ * Not served: an fp8 cache in these multi-token calls (sfa_decode_kv8_window serves one token per sequence), head_dim
+ * 256, ring-buffer caches, attention sinks, soft-capping.
  */
 int    sfa_decode_chunk_window(const sfa_decode_args *args, int num_tokens, int64_t qkv_token_stride, int window,
                                void *stream);
@@ -348,6 +351,39 @@ int    sfa_decode_varlen_window(const sfa_decode_args *args, const void *cu_toke
                                 int64_t qkv_token_stride, int window, void *stream);
 size_t sfa_decode_varlen_window_workspace_bytes(int batch_size, int num_heads, int num_heads_kv, int head_dim,
                                                 int memory_max_len, int total_tokens, int window, int num_splits);
+
+/* ---- decode with a sliding window over an fp8 KV cache ------------------------------ */
+/*
+ * sfa_decode_kv8 for a sliding-window attention layer: the conjunction of the contracts of sfa_decode_kv8 and
+ * sfa_decode_window.
+ * Everything of sfa_decode_kv8 holds unchanged: the caches are e4m3 bytes in the three layouts (strides in elements =
+ * bytes, 16-byte aligned); dtype is the dtype of qkv, the biases, the rotary tables and o; head_dim 64 or 128 (256 returns
+ * SFA_ERR_UNSUPPORTED_HEAD_DIM); k_scale / v_scale are device fp32 [num_heads_kv], 4-byte aligned, finite and > 0
+ * (not checked), NULL = 1.0; the new token is stored at row pos as k8 = q8(k16 / k_scale[hk]), v8 = q8(v16 / v_scale[hk])
+ * and attends through that quantised value; the rejection rules and the status word.
+ * The only difference is the key range.  With lo = max(0, pos + 1 - window):
+ *   o = softmax(q16 . (k_scale[hk] * K8[lo..pos])^T * head_dim_inv) . (v_scale[hk] * V8[lo..pos])     (fp32 accumulate)
+ *   window >= 1     window < 1 returns SFA_ERR_BAD_SHAPE.  window = 1 attends to the (quantised) new token only; window >
+ *                   pos for every sequence is sfa_decode_kv8, bit for bit, at the same explicit num_splits.
+ * What the window promises is what sfa_decode_window promises:
+ *   - cache rows below lo are never read and may hold anything, the NaN byte 0x7F included (as do the rows beyond pos
+ *     and the other layers);
+ *   - in a paged cache the block_table entries [0, lo / page_size) are never read and may hold any value, -1 included: a
+ *     server may free those pages;
+ *   - only a bad entry on a page that intersects [lo, pos] raises SFA_ERR_BLOCK_TABLE_RANGE (on the append page it
+ *     rejects the sequence, on a read page it makes the affected outputs NaN);
+ *   - lo is computed on the device from seq_len: the call allocates nothing, never synchronises and may be captured in
+ *     a graph and replayed with other seq_len contents.
+ * Workspace: there is no sizing function of its own.  Layout and split rule are sfa_decode_window's (num_splits <= 0:
+ * sfa_decode_auto_splits(batch_size, num_heads_kv, head_dim, min(window, memory_max_len))), and
+ * sfa_decode_window_workspace_bytes sizes it.  A workspace sized by sfa_decode_workspace_bytes_gqa is never too small;
+ * with num_splits <= 0 one that holds fewer splits than the library would pick gets the largest count it holds.  The
+ * same workspace and status word serve every decode entry point on a stream.
+ * Not served: the fp8 cache in the multi-token calls, head_dim 256, per-token or per-block scales, ring-buffer caches,
+ * attention sinks, soft-capping.
+ */
+int sfa_decode_kv8_window(const sfa_decode_args *args, const float *k_scale, const float *v_scale, int window,
+                          void *stream);
 
 /* ---- prefill: O = softmax(mask(Q K^T * scale)) V ------------------------------- */
 /*

@@ -28,6 +28,7 @@ EXPORTED_SYMBOLS = [
     "sfa_decode_window", "sfa_decode_window_workspace_bytes",
     "sfa_decode_chunk_window", "sfa_decode_chunk_window_workspace_bytes",
     "sfa_decode_varlen_window", "sfa_decode_varlen_window_workspace_bytes",
+    "sfa_decode_kv8_window",
 ]
 
 
@@ -130,6 +131,9 @@ def load():
                                              ctypes.c_int, ctypes.c_void_p]
     lib.sfa_decode_varlen_window_workspace_bytes.restype = ctypes.c_size_t
     lib.sfa_decode_varlen_window_workspace_bytes.argtypes = [ctypes.c_int] * 8
+    lib.sfa_decode_kv8_window.restype = ctypes.c_int
+    lib.sfa_decode_kv8_window.argtypes = [ctypes.POINTER(DecodeArgs), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                          ctypes.c_void_p]
     lib.sfa_prefill_fwd.restype = ctypes.c_int
     lib.sfa_prefill_fwd.argtypes = [ctypes.POINTER(PrefillArgs), ctypes.c_void_p]
     lib.sfa_compute_rotary_table.restype = ctypes.c_int

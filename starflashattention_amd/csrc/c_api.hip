@@ -142,6 +142,8 @@ constexpr EntryPoint kVarlen = {"sfa_decode_varlen", "total_tokens", false, true
 // (head_dim 256 passes the shared checks and is refused by sfa_decode_kv8 itself, with a message of its own)
 constexpr EntryPoint kKv8 = {"sfa_decode_kv8", "num_tokens", true, false, false};
 constexpr EntryPoint kWindow = {"sfa_decode_window", "num_tokens", true, false, false};
+// (head_dim 256: as kKv8)
+constexpr EntryPoint kKv8Window = {"sfa_decode_kv8_window", "num_tokens", true, false, false};
 constexpr EntryPoint kChunkWindow = {"sfa_decode_chunk_window", "num_tokens", false, true, false};
 constexpr EntryPoint kVarlenWindow = {"sfa_decode_varlen_window", "total_tokens", false, true, true};
 
@@ -429,6 +431,42 @@ int sfa_decode_window(const sfa_decode_args *a, int window, void *stream) {
     p.d.part_ml = (float2 *)(ws + w.part_ml);
     p.window = window;
     return launch_decode_window(p, a->dtype, a->head_dim, (hipStream_t)stream);
+}
+
+// sfa_decode_kv8 with a sliding window: the checks of sfa_decode_kv8 and sfa_decode_window; the workspace, its split
+// rule and the status word are sfa_decode_window's
+int sfa_decode_kv8_window(const sfa_decode_args *a, const float *k_scale, const float *v_scale, int window,
+                          void *stream) {
+    DecodeCall dc;
+    if (const int rc = validate_decode_call(kKv8Window, a, 1, 0, &dc)) return rc;
+    if (a->head_dim == 256)
+        return fail(SFA_ERR_UNSUPPORTED_HEAD_DIM,
+                    "sfa_decode_kv8_window: head_dim 256 is not supported over an fp8 cache yet (64 or 128; "
+                    "sfa_decode_window serves 256 on a 16-bit cache)");
+    if (((uintptr_t)k_scale | (uintptr_t)v_scale) & 3)
+        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_kv8_window: k_scale / v_scale must be 4-byte aligned");
+    if (window < 1) return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_kv8_window: window=%d must be >= 1", window);
+    if (a->batch_size == 0) return SFA_OK;
+
+    const size_t bh = (size_t)a->batch_size * a->num_heads;
+    // as in sfa_decode_window: a workspace sized for fewer splits than the library would pick gets the largest count it
+    // holds
+    int S = a->num_splits > 0 ? a->num_splits : window_auto_splits(a->batch_size, dc.hkv, a->memory_max_len, window);
+    if (a->num_splits <= 0 && a->workspace)
+        while (S > 1 && a->workspace_bytes < decode_workspace(0, 0, bh, S, a->head_dim).total) --S;
+    const DecodeWorkspace w = decode_workspace(0, 0, bh, S, a->head_dim);
+    if (const int rc = check_workspace(kKv8Window, a, w.total)) return rc;
+
+    Kv8WindowKernelParams p;
+    memset(&p, 0, sizeof(p));
+    p.base.d = decode_params(a, dc.hkv, dc.page_shift, S, dc.stride);
+    char *ws = (char *)a->workspace;
+    p.base.d.part_o = (float *)(ws + w.part_o);
+    p.base.d.part_ml = (float2 *)(ws + w.part_ml);
+    p.base.k_scale = k_scale;
+    p.base.v_scale = v_scale;
+    p.window = window;
+    return launch_decode_kv8_window(p, a->dtype, a->head_dim, (hipStream_t)stream);
 }
 
 int sfa_kv8_quantize(void *dst, const void *src, const float *scale, int64_t rows, int num_heads_kv, int head_dim,

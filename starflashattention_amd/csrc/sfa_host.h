@@ -84,7 +84,7 @@ struct VarlenWindowKernelParams {
     int window;
 };
 
-// sfa_decode_kv8 (decode_kv8_kernel.hip): caches of one byte per element (e4m3) with a scale per kv head.
+// sfa_decode_kv8 (decode_kv8_kernel.hip, decode_kv8_body.h): caches of one byte per element (e4m3) with a scale per kv head.
 struct Kv8KernelParams {
     DecodeKernelParams d;   // every field keeps its sfa_decode meaning; d.k_cache / d.v_cache point to bytes, the cache
                             // strides are in elements = bytes
@@ -95,6 +95,14 @@ struct Kv8KernelParams {
 // `window` positions.
 struct WindowKernelParams {
     DecodeKernelParams d;   // every field keeps its sfa_decode meaning
+    int window;             // >= 1: the token at pos attends to the rows max(0, pos + 1 - window) .. pos
+};
+
+// sfa_decode_kv8_window (decode_kv8_window_kernel.hip, the body of decode_kv8_body.h with its window): sfa_decode_kv8
+// over the last `window` positions.  The window rides behind the unchanged parameters, so decode_kv8_kernel keeps its
+// argument layout.
+struct Kv8WindowKernelParams {
+    Kv8KernelParams base;
     int window;             // >= 1: the token at pos attends to the rows max(0, pos + 1 - window) .. pos
 };
 
@@ -132,6 +140,9 @@ int launch_kv8_quantize(void *dst, const void *src, const float *scale, long lon
 // decode_window_kernel.hip: the sliding-window attention kernel (every group size; one body with launch_decode_gqa_mfma's
 // kernel, decode_mfma16.h) plus the split combine
 int launch_decode_window(const WindowKernelParams &p, int dtype, int head_dim, hipStream_t stream);
+// decode_kv8_window_kernel.hip: the sliding-window attention kernel over e4m3 caches (one body with launch_decode_kv8's
+// kernel, decode_kv8_body.h) plus the split combine
+int launch_decode_kv8_window(const Kv8WindowKernelParams &p, int dtype, int head_dim, hipStream_t stream);
 int launch_prefill(const PrefillKernelParams &p, int dtype, int head_dim, bool causal, hipStream_t stream);
 int launch_prefill_no_keys(const PrefillKernelParams &p, int head_dim, hipStream_t stream);
 int launch_rotary_table(void *cos_t, void *sin_t, int max_seq_len, int rot_dim, int dtype, hipStream_t stream);

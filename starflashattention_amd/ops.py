@@ -248,6 +248,33 @@ def flash_decode_kv8(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, 
     return o
 
 
+def flash_decode_kv8_window(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o,
+                            batch_size, memory_max_len, num_heads, head_dim, rotary_embedding_dim,
+                            max_input_length, num_layer, idx_layer, window, *, num_splits=0,
+                            rotary_cos_table=None, rotary_sin_table=None, softmax_scale=None, kv_layout="blmhd",
+                            block_table=None, num_heads_kv=None, k_scale=None, v_scale=None):
+    """flash_decode_kv8 with a sliding window (include/star_flash_attn.h, sfa_decode_kv8_window): the new token at
+    position pos = seq_len[b] is stored as q8(x / scale) and attends, through that stored value, to itself and the
+    window - 1 rows of the fp8 cache before it, lo = max(0, pos + 1 - window) .. pos.  window >= 1; the caches, the scales
+    and every other argument as in flash_decode_kv8.  Cache rows below lo, and block_table entries of pages wholly below
+    lo, are never read.  Returns `o`."""
+    lib = _lib.load()
+    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
+                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
+                                      kv_layout, block_table, num_heads_kv, kv8=True)
+    W = int(window)
+    _require(-2 ** 31 <= W < 2 ** 31, f"window={window} does not fit an int")
+    dev = qkv.device
+    ks, vs = _kv8_scale(k_scale, "k_scale", Hkv, dev), _kv8_scale(v_scale, "v_scale", Hkv, dev)
+    with torch.cuda.device(dev):
+        S = int(num_splits) if num_splits and num_splits > 0 else 0
+        ws = _workspace(dev, lib.sfa_decode_window_workspace_bytes(B, H, Hkv, D, M, W, S))
+        _call_decode(dev, a, (H + 2 * Hkv) * D, S, ws,
+                     lambda args, stream: lib.sfa_decode_kv8_window(args, ks, vs, W, stream))
+    return o
+
+
 def quantize_kv8(src, scale=None, out=None):
     """16-bit cache rows -> e4m3 bytes (include/star_flash_attn.h, sfa_kv8_quantize): out[r, h, d] = q8(src[r, h, d] /
     scale[h]).  src is a [rows, Hkv, D] fp16 / bf16 view with any row and head strides that are multiples of 16
