@@ -25,6 +25,7 @@
  *   sfa_decode_window           <- (no reference function: sfa_decode over the last `window` positions)
  *   sfa_decode_chunk_window     <- (no reference function: sfa_decode_chunk / sfa_decode_varlen with that window)
  *   sfa_decode_kv8_window       <- (no reference function: sfa_decode_kv8 over the last `window` positions)
+ *   sfa_decode_chunk_kv8        <- (no reference function: sfa_decode_chunk / sfa_decode_varlen over an fp8 KV cache)
  * The Python-facing mha_fwd_cuda (src/flash_api.cpp:42-68) and the C++ template
  * surface (src/flash_attn.h) in this repo are thin layers over these symbols.
  */
@@ -51,7 +52,9 @@ extern "C" {
  *      beside an unchanged sfa_decode_args: callers detect them by symbol
  *      sfa_decode_chunk_window, sfa_decode_varlen_window and their _workspace_bytes functions (the sliding window in the
  *      multi-token calls) added under the same version, in the same way
- *      sfa_decode_kv8_window (the sliding window over an fp8 KV cache) added under the same version, in the same way */
+ *      sfa_decode_kv8_window (the sliding window over an fp8 KV cache) added under the same version, in the same way
+ *      sfa_decode_chunk_kv8 and sfa_decode_varlen_kv8 (the multi-token calls over an fp8 KV cache) added under the same
+ *      version, in the same way; they have no sizing functions of their own */
 #define SFA_ABI_VERSION 4
 
 typedef enum sfa_status {
@@ -272,8 +275,10 @@ size_t sfa_decode_varlen_workspace_bytes(int batch_size, int num_heads, int num_
 int sfa_decode_kv8(const sfa_decode_args *args, const float *k_scale, const float *v_scale, void *stream);
 
 /*
- * How a prompt gets into an fp8 cache: it runs through sfa_decode_chunk / sfa_decode_varlen on a 16-bit staging cache
- * (one layer of it is enough), then its rows are quantised into the fp8 cache:
+ * 16-bit cache rows -> rows of an fp8 cache.  A prompt gets into an fp8 cache directly through sfa_decode_chunk_kv8 /
+ * sfa_decode_varlen_kv8 (below).  The alternative this function serves: the prompt runs through sfa_decode_chunk /
+ * sfa_decode_varlen on a 16-bit staging cache (one layer of it is enough) -- its tokens then attend through their 16-bit
+ * values -- and its rows are quantised into the fp8 cache afterwards:
  *   dst[r*dst_row_stride + h*dst_head_stride + d] = q8(src[r*src_row_stride + h*src_head_stride + d] / scale[h])
  * for r < rows, h < num_heads_kv, d < head_dim (64 or 128); rows = 0 does nothing.  src holds `dtype` (fp16 / bf16)
  * elements, dst bytes.  Strides are in elements and multiples of 16, dst and src 16-byte aligned; scale is device fp32
@@ -340,8 +345,9 @@ size_t sfa_decode_window_workspace_bytes(int batch_size, int num_heads, int num_
  * sfa_decode_chunk_workspace_bytes / sfa_decode_varlen_workspace_bytes is never too small; one that holds fewer splits
  * than the library would pick gets the largest count it holds.  The split key range is the tiles that hold
  * [lo_0, pos + n), not [0, pos + n): a short window over a long history is shared by all splits.
- * Not served: an fp8 cache in these multi-token calls (sfa_decode_kv8_window serves one token per sequence), head_dim
- * 256, ring-buffer caches, attention sinks, soft-capping.
+ * Not served: an fp8 cache in these windowed multi-token calls (sfa_decode_kv8_window serves one token per sequence,
+ * sfa_decode_chunk_kv8 / sfa_decode_varlen_kv8 the whole history), head_dim 256, ring-buffer caches, attention sinks,
+ * soft-capping.
  */
 int    sfa_decode_chunk_window(const sfa_decode_args *args, int num_tokens, int64_t qkv_token_stride, int window,
                                void *stream);
@@ -379,11 +385,46 @@ size_t sfa_decode_varlen_window_workspace_bytes(int batch_size, int num_heads, i
  * sfa_decode_window_workspace_bytes sizes it.  A workspace sized by sfa_decode_workspace_bytes_gqa is never too small;
  * with num_splits <= 0 one that holds fewer splits than the library would pick gets the largest count it holds.  The
  * same workspace and status word serve every decode entry point on a stream.
- * Not served: the fp8 cache in the multi-token calls, head_dim 256, per-token or per-block scales, ring-buffer caches,
- * attention sinks, soft-capping.
+ * Not served: a sliding window over the fp8 cache in the multi-token calls (sfa_decode_chunk_kv8 / sfa_decode_varlen_kv8
+ * attend to the whole history), head_dim 256, per-token or per-block scales, ring-buffer caches, attention sinks,
+ * soft-capping.
  */
 int sfa_decode_kv8_window(const sfa_decode_args *args, const float *k_scale, const float *v_scale, int window,
                           void *stream);
+
+/* ---- multi-token decode over an fp8 KV cache ---------------------------------------- */
+/*
+ * sfa_decode_chunk / sfa_decode_varlen over the e4m3 caches of sfa_decode_kv8: the call gives exactly what n successive
+ * sfa_decode_kv8 calls would.  It is the conjunction of two contracts.
+ * Everything of sfa_decode_chunk / sfa_decode_varlen holds unchanged: the qkv / o shapes and strides, bias, RoPE at
+ * pos + t, the rotary tables, partial rotary, every kv_layout, num_heads / num_heads_kv in {1, 2, 4, 8, 16}, fp16 / bf16,
+ * head_dim 64 / 128 (256 returns SFA_ERR_UNSUPPORTED_HEAD_DIM), the cu_tokens rules and n_b == 0, the rejection rules
+ * and the status word; seq_len is not incremented; the call allocates nothing, never synchronises and may be captured
+ * in a graph and replayed with other seq_len / cu_tokens contents.
+ * Everything of sfa_decode_kv8 holds unchanged: the caches are e4m3 bytes in the three layouts (strides in elements =
+ * bytes, 16-byte aligned); dtype is the dtype of qkv, the biases, the rotary tables and o; k_scale / v_scale are device
+ * fp32 [num_heads_kv], 4-byte aligned (checked), finite and > 0 (not checked), NULL = 1.0.
+ * Semantics, for token t of a sequence at pos = seq_len[b] and every kv head hk:
+ *   k16, v16 = exactly what sfa_decode_chunk would have stored at row pos + t
+ *   k8 = q8(k16 / k_scale[hk]),  v8 = q8(v16 / v_scale[hk])     written at row pos + t; no other byte of a cache changes
+ *   o = softmax(q16 . (k_scale[hk] * K8[0..pos+t])^T * head_dim_inv) . (v_scale[hk] * V8[0..pos+t])    (fp32 accumulate)
+ * over the cache AFTER the append: token t sees the new rows 0..t, its own included, through their quantised values,
+ * so the output is a function of the cache bytes after the call.  (Through a 16-bit staging cache and sfa_kv8_quantize
+ * the new tokens attend through their 16-bit values instead: n draft tokens verified that way do not get what n
+ * sfa_decode_kv8 steps give them.)
+ * Rows at and beyond pos + n, the other layers and spare pages are never read and may hold anything, the NaN byte 0x7F
+ * included.
+ * Workspace: there are no sizing functions of their own.  Layout, split rule and status word are those of
+ * sfa_decode_chunk / sfa_decode_varlen, and sfa_decode_chunk_workspace_bytes / sfa_decode_varlen_workspace_bytes size
+ * it.  (The split rule was tuned on 16-bit rows and has not been re-tuned for one-byte rows.)  The same workspace and
+ * status word serve every decode entry point on a stream.
+ * Not served: a sliding window over the fp8 cache in these calls, head_dim 256, per-token or per-block scales, fp8
+ * matrix instructions on a quantised Q.
+ */
+int sfa_decode_chunk_kv8(const sfa_decode_args *args, const float *k_scale, const float *v_scale, int num_tokens,
+                         int64_t qkv_token_stride, void *stream);
+int sfa_decode_varlen_kv8(const sfa_decode_args *args, const float *k_scale, const float *v_scale,
+                          const void *cu_tokens, int total_tokens, int64_t qkv_token_stride, void *stream);
 
 /* ---- prefill: O = softmax(mask(Q K^T * scale)) V ------------------------------- */
 /*

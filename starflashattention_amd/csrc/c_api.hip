@@ -146,6 +146,8 @@ constexpr EntryPoint kWindow = {"sfa_decode_window", "num_tokens", true, false, 
 constexpr EntryPoint kKv8Window = {"sfa_decode_kv8_window", "num_tokens", true, false, false};
 constexpr EntryPoint kChunkWindow = {"sfa_decode_chunk_window", "num_tokens", false, true, false};
 constexpr EntryPoint kVarlenWindow = {"sfa_decode_varlen_window", "total_tokens", false, true, true};
+constexpr EntryPoint kChunkKv8 = {"sfa_decode_chunk_kv8", "num_tokens", false, true, false};
+constexpr EntryPoint kVarlenKv8 = {"sfa_decode_varlen_kv8", "total_tokens", false, true, true};
 
 // What the entry points check alike, before any HIP call, and what they derive on the way.  sfa_decode is the case of
 // one token per sequence (count = 1) with no token stride.
@@ -573,6 +575,29 @@ int sfa_decode_chunk_window(const sfa_decode_args *a, int num_tokens, int64_t qk
     return launch_decode_chunk_window(p, a->dtype, a->head_dim, (hipStream_t)stream);
 }
 
+// sfa_decode_chunk over e4m3 caches: the checks of sfa_decode_chunk and the scale check of sfa_decode_kv8; the workspace,
+// its split rule (tuned on 16-bit rows and not re-tuned for one-byte rows) and the status word are sfa_decode_chunk's
+int sfa_decode_chunk_kv8(const sfa_decode_args *a, const float *k_scale, const float *v_scale, int num_tokens,
+                         int64_t qkv_token_stride, void *stream) {
+    DecodeCall dc;
+    if (const int rc = validate_decode_call(kChunkKv8, a, num_tokens, qkv_token_stride, &dc)) return rc;
+    if (((uintptr_t)k_scale | (uintptr_t)v_scale) & 3)
+        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk_kv8: k_scale / v_scale must be 4-byte aligned");
+    if (a->batch_size == 0 || num_tokens == 0) return SFA_OK;
+
+    const int rows = num_tokens * dc.group;
+    const int S = a->num_splits > 0 ? a->num_splits : chunk_auto_splits(a->batch_size, dc.hkv, rows, a->memory_max_len);
+    const DecodeWorkspace w = chunk_workspace(a->batch_size, dc.hkv, rows, S, a->head_dim);
+    if (const int rc = check_workspace(kChunkKv8, a, w.total)) return rc;
+
+    ChunkKv8KernelParams p;
+    memset(&p, 0, sizeof(p));
+    p.base = chunk_params(a, dc, num_tokens, S, w);
+    p.k_scale = k_scale;
+    p.v_scale = v_scale;
+    return launch_decode_chunk_kv8(p, a->dtype, a->head_dim, (hipStream_t)stream);
+}
+
 // (rows = total_tokens * group packed query rows per kv head)
 static DecodeWorkspace varlen_workspace(int B, int hkv, long long rows, int S, int D) {
     const size_t hr = (size_t)hkv * rows;
@@ -655,6 +680,21 @@ int sfa_decode_varlen_window(const sfa_decode_args *a, const void *cu_tokens, in
     if (!p.base.cu_tokens) return SFA_OK;       // nothing to do
     p.window = window;
     return launch_decode_varlen_window(p, a->dtype, a->head_dim, (hipStream_t)stream);
+}
+
+// sfa_decode_varlen over e4m3 caches: as sfa_decode_chunk_kv8 is to sfa_decode_chunk
+int sfa_decode_varlen_kv8(const sfa_decode_args *a, const float *k_scale, const float *v_scale, const void *cu_tokens,
+                          int total_tokens, int64_t qkv_token_stride, void *stream) {
+    VarlenKv8KernelParams p;
+    memset(&p, 0, sizeof(p));
+    // (before varlen_call, whose last check is the workspace: as in sfa_decode_kv8 the scales are checked before it)
+    if (((uintptr_t)k_scale | (uintptr_t)v_scale) & 3)
+        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_varlen_kv8: k_scale / v_scale must be 4-byte aligned");
+    if (const int rc = varlen_call(kVarlenKv8, a, cu_tokens, total_tokens, qkv_token_stride, false, 0, &p.base)) return rc;
+    if (!p.base.cu_tokens) return SFA_OK;       // nothing to do
+    p.k_scale = k_scale;
+    p.v_scale = v_scale;
+    return launch_decode_varlen_kv8(p, a->dtype, a->head_dim, (hipStream_t)stream);
 }
 
 int sfa_prefill_fwd(const sfa_prefill_args *a, void *stream) {

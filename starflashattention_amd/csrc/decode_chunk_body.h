@@ -20,8 +20,15 @@
 // A sliding window (sfa_decode_chunk_window / sfa_decode_varlen_window) is a compile-time property of the geometry:
 // WindowGeo<BASE, P> below is BASE with `static constexpr bool kWindow = true` and window(gp).  Only chunk_attn_kernel
 // looks at it; without the flag none of the window's code is compiled.
+//
+// An fp8 (e4m3) KV cache (sfa_decode_chunk_kv8 / sfa_decode_varlen_kv8) is the same kind of property: Kv8Geo<BASE, P> is
+// BASE with `static constexpr bool kKv8 = true`, k_scale(gp) and v_scale(gp).  The prologue then stores q8(x / scale)
+// bytes, the attention kernel stages bytes and converts them on their way into the same 16-bit LDS tiles, and the scales
+// go into the score scale and the epilogue; the combine kernel does not look at the flag.  Without it none of the fp8
+// code is compiled.
 #pragma once
 #include "decode_chunk_common.h"
+#include "kv8_convert.h"
 #include "prefill_core.h"
 
 namespace sfa {
@@ -30,6 +37,8 @@ namespace chunk {
 using namespace prefill;
 using decode::pack8;
 using decode::unpack8;
+using decode::dq8;
+using decode::q8x8;
 
 constexpr uint16_t nan_bits(int dtype_id) { return dtype_id == 0 ? 0x7e00 : 0x7fc0; }
 
@@ -37,12 +46,14 @@ constexpr uint16_t nan_bits(int dtype_id) { return dtype_id == 0 ? 0x7e00 : 0x7f
 template <class GEO, class = void> struct geo_window : std::false_type {};
 template <class GEO> struct geo_window<GEO, std::void_t<decltype(GEO::kWindow)>> : std::bool_constant<GEO::kWindow> {};
 
-// BASE with a window: P holds BASE's Params as `base` and the window (>= 1) as `window`
+// Is GEO's cache e4m3 bytes with a scale per kv head?
+template <class GEO, class = void> struct geo_kv8 : std::false_type {};
+template <class GEO> struct geo_kv8<GEO, std::void_t<decltype(GEO::kKv8)>> : std::bool_constant<GEO::kKv8> {};
+
+// BASE behind a parameter struct P that holds BASE's Params as `base`: what the wrappers below share
 template <class BASE, class P>
-struct WindowGeo {
+struct ForwardGeo {
     using Params = P;
-    static constexpr bool kWindow = true;
-    static __device__ __forceinline__ int window(const P &gp) { return gp.window; }
     static __device__ __forceinline__ const ChunkKernelParams &chunk(const P &gp) { return BASE::chunk(gp.base); }
     static __device__ __forceinline__ bool prologue(const P &gp, int &b, int &t, int &n) {
         return BASE::prologue(gp.base, b, t, n);
@@ -64,6 +75,21 @@ struct WindowGeo {
     }
 };
 
+// BASE with a window: P holds BASE's Params as `base` and the window (>= 1) as `window`
+template <class BASE, class P>
+struct WindowGeo : ForwardGeo<BASE, P> {
+    static constexpr bool kWindow = true;
+    static __device__ __forceinline__ int window(const P &gp) { return gp.window; }
+};
+
+// BASE over e4m3 caches: P holds BASE's Params as `base` and the per-kv-head scales (nullptr = 1.0) as `k_scale`, `v_scale`
+template <class BASE, class P>
+struct Kv8Geo : ForwardGeo<BASE, P> {
+    static constexpr bool kKv8 = true;
+    static __device__ __forceinline__ const float *k_scale(const P &gp) { return gp.k_scale; }
+    static __device__ __forceinline__ const float *v_scale(const P &gp) { return gp.v_scale; }
+};
+
 // The window's lower mask of a half-tile of fresh scores (mask_half's register layout): keys below lo get -inf
 __device__ __forceinline__ void mask_low(f32x16 &s, int kbase, int h2, int lo) {
 #pragma unroll
@@ -77,6 +103,7 @@ chunk_prologue_kernel(const typename GEO::Params gp) {
     const ChunkKernelParams &cp = GEO::chunk(gp);
     const DecodeKernelParams &p = cp.d;
     constexpr int LPR = D / 8;                  // lanes (16 B each) per head row
+    constexpr bool KV8 = geo_kv8<GEO>::value;   // the caches hold e4m3 bytes: strides and offsets in elements = bytes
     int t, b, n;
     if (!GEO::prologue(gp, b, t, n)) return;
     const int pos = p.seq_len[b];
@@ -99,6 +126,12 @@ chunk_prologue_kernel(const typename GEO::Params gp) {
     __shared__ float cs[D / 2], sn[D / 2];
     for (int j = threadIdx.x; j < (p.rot_dim >> 1); j += blockDim.x) chunk::rope_cs<Tr>(j, row, p, cs[j], sn[j]);
     __syncthreads();
+    // KV8: 8 values -> q8(x / scale[h]), the 8 bytes at element offset `off` of an e4m3 cache
+    auto store8 = [&](uint16_t *cache, long long off, const uint4 &pk, const float *scales, int h) {
+        float x[8];
+        unpack8<Tr>(pk, x);
+        *reinterpret_cast<uint2 *>(reinterpret_cast<char *>(cache) + off) = q8x8(x, scales ? scales[h] : 1.0f);
+    };
     const int items = (Hq + 2 * Hkv) * LPR;
     for (int i = threadIdx.x; i < items; i += blockDim.x) {
         const int hd = i / LPR, sub = i % LPR;
@@ -115,6 +148,8 @@ chunk_prologue_kernel(const typename GEO::Params gp) {
             if (isq) {
                 const long long r = (long long)t * G + h % G;
                 *reinterpret_cast<uint4 *>(cp.q_rot + GEO::q_row(gp, b, h / G, r) * D + sub * 8) = pk;
+            } else if constexpr (KV8) {           // the rounded 16-bit k the 16-bit call stores, quantised
+                store8(p.k_cache, kv_off + (long long)h * p.kv_head_stride + sub * 8, pk, GEO::k_scale(gp), h);
             } else {
                 *reinterpret_cast<uint4 *>(p.k_cache + kv_off + (long long)h * p.kv_head_stride + sub * 8) = pk;
             }
@@ -127,7 +162,10 @@ chunk_prologue_kernel(const typename GEO::Params gp) {
                 chunk::add_bias8<Tr>(x, p.v_bias + (long long)h * D + sub * 8);
                 pk = pack8<Tr>(x);
             }
-            *reinterpret_cast<uint4 *>(p.v_cache + kv_off + (long long)h * p.kv_head_stride + sub * 8) = pk;
+            if constexpr (KV8)
+                store8(p.v_cache, kv_off + (long long)h * p.kv_head_stride + sub * 8, pk, GEO::v_scale(gp), h);
+            else
+                *reinterpret_cast<uint4 *>(p.v_cache + kv_off + (long long)h * p.kv_head_stride + sub * 8) = pk;
         }
     }
 }
@@ -142,7 +180,14 @@ chunk_attn_kernel(const typename GEO::Params gp) {
     constexpr int NKS = D / 16;                 // k-steps of Q.K^T
     constexpr int NDB = D / 32;                 // 32-wide d blocks of O^T
     constexpr int NPV_ = 2 * NDB;
-    constexpr int CPR = D / 8;                  // 16-B chunks per row
+    // A staged chunk is CE elements of a cache row: 16 B of a 16-bit cache.  KV8 (EB = 1 byte per element): 16 B at
+    // head_dim 128 and 8 B at head_dim 64, so that the 64 rows of a tile are one load per thread either way; the chunk
+    // becomes 2 * CE bytes of the 16-bit LDS image at store_op.
+    constexpr bool KV8 = geo_kv8<GEO>::value;
+    constexpr int EB = KV8 ? 1 : 2;             // bytes per cache element
+    constexpr int CE = KV8 && D == 128 ? 16 : 8;
+    constexpr int CBG = CE * EB, CBL = CE * 2;  // bytes of a chunk in the cache / in LDS
+    constexpr int CPR = D / CE;                 // chunks per row
     constexpr int NLD = kBN * CPR / kThreads;   // chunks staged per thread per tile (2 or 1)
     constexpr int ROWSTEP = kThreads / CPR;     // row distance between a thread's chunks
     constexpr int NPS = PAGED ? 4 : 1;          // page slots of a 64-row tile (page_size >= 16)
@@ -225,14 +270,31 @@ chunk_attn_kernel(const typename GEO::Params gp) {
 
     // ---- staging: thread owns chunks (row st_row + i*ROWSTEP, chunk st_ch), i < NLD, of every tile ----
     const int st_row = tid / CPR, st_ch = tid % CPR;
-    const long long rsb = 2 * p.kv_row_stride;  // bytes between cache rows (of one page)
+    const long long rsb = EB * p.kv_row_stride; // bytes between cache rows (of one page)
     const long long hb = chunk::head_base<D, PAGED>(p, b, hk);
-    const char *const kg = reinterpret_cast<const char *>(p.k_cache + hb);
-    const char *const vg = reinterpret_cast<const char *>(p.v_cache + hb);
-    char *const k_w = smem + L::KS * st_row + 16 * st_ch;
-    char *const v_w = smem + L::V_BASE + L::VS * st_row + 16 * st_ch;
+    const char *const kg = reinterpret_cast<const char *>(p.k_cache) + EB * hb;
+    const char *const vg = reinterpret_cast<const char *>(p.v_cache) + EB * hb;
+    char *const k_w = smem + L::KS * st_row + CBL * st_ch;
+    char *const v_w = smem + L::V_BASE + L::VS * st_row + CBL * st_ch;
     uint4 kr0, kr1, vr0, vr1;       // plain scalars: arrays of these ended up in scratch (prefill_kernel.hip)
     kr0 = kr1 = vr0 = vr1 = make_uint4(0, 0, 0, 0);
+    // a chunk from the cache (KV8: raw bytes, CBG of them) and into an LDS tile (KV8: converted, exact in both types)
+    auto ld_chunk = [](const char *src) -> uint4 {
+        if constexpr (CBG == 8) {
+            const uint2 v = *reinterpret_cast<const uint2 *>(src);
+            return make_uint4(v.x, v.y, 0, 0);
+        } else {
+            return *reinterpret_cast<const uint4 *>(src);
+        }
+    };
+    auto st_chunk = [](char *dst, const uint4 &r) {
+        if constexpr (KV8) {
+            *reinterpret_cast<uint4 *>(dst) = dq8<Tr>(r.x, r.y);
+            if constexpr (CE == 16) *reinterpret_cast<uint4 *>(dst + 16) = dq8<Tr>(r.z, r.w);
+        } else {
+            *reinterpret_cast<uint4 *>(dst) = r;
+        }
+    };
     // Rows of a tile: contiguous layouts and pages >= 64 rows hold the whole tile at one base; pages of 16 / 32 rows
     // split it into 4 / 2 page slots of 1 << psh rows.  Row r of the tile is at slot base (r >> psh) plus the
     // lane offset (r & (2^psh - 1)) * rsb.  The ragged last tile (Kb % 64 != 0) swaps in row-clamped offsets.
@@ -247,7 +309,7 @@ chunk_attn_kernel(const typename GEO::Params gp) {
     const int row0_ = st_row, row1_ = st_row + ROWSTEP;
     const int rr0_ = min(row0_, last0), rr1_ = min(row1_, last0);
     // (32 bit: 64 rows * rsb < 2^31, checked by sfa_decode_chunk)
-    auto lane_off = [&](int r) -> unsigned { return (unsigned)(r & rmask) * (unsigned)rsb + 16u * st_ch; };
+    auto lane_off = [&](int r) -> unsigned { return (unsigned)(r & rmask) * (unsigned)rsb + (unsigned)CBG * st_ch; };
     const unsigned ow0 = lane_off(row0_), ow1 = lane_off(row1_), or0 = lane_off(rr0_), or1 = lane_off(rr1_);
     const int sw0 = row0_ >> psh, sw1 = row1_ >> psh, sr0 = rr0_ >> psh, sr1 = rr1_ >> psh;
     const int32_t *tbl = PAGED ? p.block_table + (long long)b * p.table_stride : nullptr;
@@ -270,7 +332,7 @@ chunk_attn_kernel(const typename GEO::Params gp) {
                     bad_page = 1;
                     pg = 0;
                 }
-                o[j] = pg * p.page_stride * 2 + (long long)(r0 & pmask) * rsb;
+                o[j] = pg * p.page_stride * EB + (long long)(r0 & pmask) * rsb;
             }
         }
     };
@@ -299,16 +361,16 @@ chunk_attn_kernel(const typename GEO::Params gp) {
         return sel(o, r >> psh) + lane_off(r);
     };
     auto ld_k = [&](const TileSrc &ts, int i) -> uint4 {
-        if constexpr (WIN) return *reinterpret_cast<const uint4 *>(kg + win_off(ts.k, i, ts.fk, ts.rk));
+        if constexpr (WIN) return ld_chunk(kg + win_off(ts.k, i, ts.fk, ts.rk));
         const long long off = i == 0 ? (ts.rk ? sel(ts.k, sr0) + or0 : sel(ts.k, sw0) + ow0)
                                      : (ts.rk ? sel(ts.k, sr1) + or1 : sel(ts.k, sw1) + ow1);
-        return *reinterpret_cast<const uint4 *>(kg + off);
+        return ld_chunk(kg + off);
     };
     auto ld_v = [&](const TileSrc &ts, int i) -> uint4 {
-        if constexpr (WIN) return *reinterpret_cast<const uint4 *>(vg + win_off(ts.v, i, ts.fv, ts.rv));
+        if constexpr (WIN) return ld_chunk(vg + win_off(ts.v, i, ts.fv, ts.rv));
         const long long off = i == 0 ? (ts.rv ? sel(ts.v, sr0) + or0 : sel(ts.v, sw0) + ow0)
                                      : (ts.rv ? sel(ts.v, sr1) + or1 : sel(ts.v, sw1) + ow1);
-        return *reinterpret_cast<const uint4 *>(vg + off);
+        return ld_chunk(vg + off);
     };
     auto load_op = [&](int n, const TileSrc &ts) {
         if (n == 0) kr0 = ld_k(ts, 0);
@@ -317,13 +379,19 @@ chunk_attn_kernel(const typename GEO::Params gp) {
         if (NLD > 1 && n == 3) vr1 = ld_v(ts, 1);
     };
     auto store_op = [&](int n, int kbuf, int vbuf) {
-        if (n == 0) *reinterpret_cast<uint4 *>(k_w + kbuf) = kr0;
-        if (n == 1) *reinterpret_cast<uint4 *>(v_w + vbuf) = vr0;
-        if (NLD > 1 && n == 2) *reinterpret_cast<uint4 *>(k_w + kbuf + ROWSTEP * L::KS) = kr1;
-        if (NLD > 1 && n == 3) *reinterpret_cast<uint4 *>(v_w + vbuf + ROWSTEP * L::VS) = vr1;
+        if (n == 0) st_chunk(k_w + kbuf, kr0);
+        if (n == 1) st_chunk(v_w + vbuf, vr0);
+        if (NLD > 1 && n == 2) st_chunk(k_w + kbuf + ROWSTEP * L::KS, kr1);
+        if (NLD > 1 && n == 3) st_chunk(v_w + vbuf + ROWSTEP * L::VS, vr1);
     };
 
-    const float c2 = p.scale_log2;
+    // KV8: the scales never touch a tile -- k_scale[hk] goes into the score scale, v_scale[hk] into the epilogue
+    float ksc = 1.0f, vsc = 1.0f;
+    if constexpr (KV8) {
+        if (GEO::k_scale(gp)) ksc = GEO::k_scale(gp)[hk];
+        if (GEO::v_scale(gp)) vsc = GEO::v_scale(gp)[hk];
+    }
+    const float c2 = KV8 ? p.scale_log2 * ksc : p.scale_log2;
     const char *const k_rd = smem + L::KS * l31 + 16 * h2;                 // K row l31, chunk h2
     const char *const v_rd = smem + L::V_BASE + L::VS * (4 * h2 + ((lane & 15) >> 2)) +
                              32 * ((lane >> 4) & 1) + 16 * ((lane & 3) >> 1) + 8 * (lane & 1);
@@ -361,8 +429,8 @@ chunk_attn_kernel(const typename GEO::Params gp) {
         for (int ks = 0; ks < NKS; ++ks) asm volatile("" : "+v"(qf[0][ks]));   // launder: prefill_kernel.hip
 #pragma unroll
         for (int n = 0; n < NOPS; ++n) store_op(n, 0, 0);
-        *reinterpret_cast<uint4 *>(k_w + L::KTILE) = kx0;
-        if (NLD > 1) *reinterpret_cast<uint4 *>(k_w + L::KTILE + ROWSTEP * L::KS) = kx1;
+        st_chunk(k_w + L::KTILE, kx0);
+        if (NLD > 1) st_chunk(k_w + L::KTILE + ROWSTEP * L::KS, kx1);
         __syncthreads();
         {
             const TileSrc ts1 = tile_src(2, 1);
@@ -469,10 +537,16 @@ chunk_attn_kernel(const typename GEO::Params gp) {
     if (qrow < R) {
         if (S == 1) {
             // every row sees key 0 (pos >= 0; WIN: its own key), so ltot > 0 -- or NaN after a bad page
-            store_o_row<Tr, D>(out_row(qrow), acc.o[0], 1.0f / ltot, h2);
+            store_o_row<Tr, D>(out_row(qrow), acc.o[0], (KV8 ? vsc : 1.0f) / ltot, h2);
         } else {
             // un-normalised O^T: lane (l31, h2) holds columns 32d + 8g + 4*h2 + {0..3} in registers 4g..4g+3
             float *po = p.part_o + (prow + qrow) * D;
+            if constexpr (KV8) {                // v_scale once, on the fp32 accumulator: the combine is the 16-bit call's
+#pragma unroll
+                for (int d = 0; d < NDB; ++d)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc.o[0][d][r] *= vsc;
+            }
 #pragma unroll
             for (int d = 0; d < NDB; ++d)
 #pragma unroll

@@ -1,8 +1,9 @@
 // The body of the matrix-core decode kernels over e4m3 caches, from the rejection to the merge of the waves: ONE copy for
 // decode_kv8_kernel.hip (sfa_decode_kv8: the whole history) and decode_kv8_window_kernel.hip (sfa_decode_kv8_window), as
-// decode_mfma16.h is for the 16-bit pair.  It is what decode_mfma_common.h leaves to the fp8 kernels: the e4m3
-// conversions, the byte loads of a tile, their staging into the wave's LDS tiles, the software pipeline (kInFlight), the
-// quantisation of the new token and its append.  The design is described in decode_kv8_kernel.hip.
+// decode_mfma16.h is for the 16-bit pair.  It is what decode_mfma_common.h leaves to the fp8 kernels: the byte loads of
+// a tile, their staging into the wave's LDS tiles, the software pipeline (kInFlight), the quantisation of the new token
+// and its append (the e4m3 conversions themselves are kv8_convert.h, shared with the multi-token step over an fp8
+// cache).  The design is described in decode_kv8_kernel.hip.
 //
 // WINDOW: the token sees the rows [lo, pos), lo = max(0, pos + 1 - window), instead of [0, pos), exactly as in
 // decode_mfma16.h:
@@ -14,48 +15,10 @@
 // Without WINDOW `window` is not looked at and no lower bound is computed anywhere.
 #pragma once
 #include "decode_mfma_common.h"
+#include "kv8_convert.h"
 
 namespace sfa {
 namespace decode {
-
-// ---- e4m3 <-> 16 bit ----------------------------------------------------------------------------------------------
-// two e4m3 bytes (the low or the high half of w) -> two 16-bit values, exact
-template <class Tr, bool HI> __device__ __forceinline__ uint32_t dq2(uint32_t w);
-template <> __device__ __forceinline__ uint32_t dq2<Bf16, false>(uint32_t w) {
-    return bitcast<uint32_t>(__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, false));
-}
-template <> __device__ __forceinline__ uint32_t dq2<Bf16, true>(uint32_t w) {
-    return bitcast<uint32_t>(__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, true));
-}
-template <> __device__ __forceinline__ uint32_t dq2<Fp16, false>(uint32_t w) {
-    return bitcast<uint32_t>(__builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, false));
-}
-template <> __device__ __forceinline__ uint32_t dq2<Fp16, true>(uint32_t w) {
-    return bitcast<uint32_t>(__builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, true));
-}
-// 8 bytes -> 8 16-bit values
-template <class Tr> __device__ __forceinline__ uint4 dq8(uint32_t a, uint32_t b) {
-    return make_uint4(dq2<Tr, false>(a), dq2<Tr, true>(a), dq2<Tr, false>(b), dq2<Tr, true>(b));
-}
-
-// q8 of four values: clamp to +-448 in fp32 (so the conversion's own overflow mode never matters), round to the nearest
-// e4m3 with ties to even, NaN -> 0x7F
-__device__ __forceinline__ uint32_t q8x4(float a, float b, float c, float d) {
-    auto cl = [](float x) { return fminf(fmaxf(x, -448.f), 448.f); };
-    int w = __builtin_amdgcn_cvt_pk_fp8_f32(cl(a), cl(b), 0, false);
-    w = __builtin_amdgcn_cvt_pk_fp8_f32(cl(c), cl(d), w, true);
-    uint32_t u = (uint32_t)w;
-    if (a != a) u = (u & 0xffffff00u) | 0x0000007fu;
-    if (b != b) u = (u & 0xffff00ffu) | 0x00007f00u;
-    if (c != c) u = (u & 0xff00ffffu) | 0x007f0000u;
-    if (d != d) u = (u & 0x00ffffffu) | 0x7f000000u;
-    return u;
-}
-// q8(x[j] / scale) for 8 values (the division is the correctly rounded fp32 one)
-__device__ __forceinline__ uint2 q8x8(const float (&x)[8], float scale) {
-    return make_uint2(q8x4(x[0] / scale, x[1] / scale, x[2] / scale, x[3] / scale),
-                      q8x4(x[4] / scale, x[5] / scale, x[6] / scale, x[7] / scale));
-}
 
 constexpr int kInFlight = 2;                    // tiles a wave keeps in flight in registers (3 measured no better, and
                                                 // 20-30 % slower through a paged cache: DESIGN.md 5.8)

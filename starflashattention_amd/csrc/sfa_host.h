@@ -91,6 +91,18 @@ struct Kv8KernelParams {
     const float *k_scale, *v_scale;     // [Hkv] each, nullptr = 1.0
 };
 
+// sfa_decode_chunk_kv8 / sfa_decode_varlen_kv8 (decode_chunk_kv8_kernel.hip, decode_varlen_kv8_kernel.hip): the chunk and
+// varlen calls over e4m3 caches.  As in Kv8KernelParams the cache pointers of `base` point to bytes and the cache strides
+// are in elements = bytes; the scales ride behind the unchanged parameters, as the window does above.
+struct ChunkKv8KernelParams {
+    ChunkKernelParams base;
+    const float *k_scale, *v_scale;     // [Hkv] each, nullptr = 1.0
+};
+struct VarlenKv8KernelParams {
+    VarlenKernelParams base;
+    const float *k_scale, *v_scale;
+};
+
 // sfa_decode_window (decode_window_kernel.hip, the body of decode_mfma16.h with its window): sfa_decode over the last
 // `window` positions.
 struct WindowKernelParams {
@@ -132,6 +144,8 @@ int launch_decode_chunk(const ChunkKernelParams &p, int dtype, int head_dim, hip
 int launch_decode_varlen(const VarlenKernelParams &p, int dtype, int head_dim, hipStream_t stream);
 int launch_decode_chunk_window(const ChunkWindowKernelParams &p, int dtype, int head_dim, hipStream_t stream);
 int launch_decode_varlen_window(const VarlenWindowKernelParams &p, int dtype, int head_dim, hipStream_t stream);
+int launch_decode_chunk_kv8(const ChunkKv8KernelParams &p, int dtype, int head_dim, hipStream_t stream);
+int launch_decode_varlen_kv8(const VarlenKv8KernelParams &p, int dtype, int head_dim, hipStream_t stream);
 // decode_kv8_kernel.hip: the attention kernel over e4m3 caches plus the split combine; the 16-bit -> e4m3 row copy
 int launch_decode_kv8(const Kv8KernelParams &p, int dtype, int head_dim, hipStream_t stream);
 int launch_kv8_quantize(void *dst, const void *src, const float *scale, long long rows, int Hkv, int head_dim,

@@ -17,6 +17,8 @@ libStarFlashAttention.so.  The public operators:
                       (new entry point).
   flash_decode_chunk_window(...) / flash_decode_varlen_window(...)  flash_decode_chunk / flash_decode_varlen with that
                       window: what n successive flash_decode_window calls give (new entry points).
+  flash_decode_chunk_kv8(...) / flash_decode_varlen_kv8(...)  flash_decode_chunk / flash_decode_varlen over an fp8 KV
+                      cache: what n successive flash_decode_kv8 calls give (new entry points).
 """
 import ctypes
 import math
@@ -356,6 +358,60 @@ def flash_decode_varlen(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_tabl
         ws = _workspace(dev, lib.sfa_decode_varlen_workspace_bytes(B, H, Hkv, D, M, T, S))
         cu = ctypes.c_void_p(cu_tokens.data_ptr())
         _call_decode(dev, a, 0, S, ws, lambda args, stream: lib.sfa_decode_varlen(args, cu, T, 0, stream))
+    return o
+
+
+def flash_decode_chunk_kv8(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o,
+                           batch_size, memory_max_len, num_heads, head_dim, rotary_embedding_dim,
+                           max_input_length, num_layer, idx_layer, *, num_splits=0,
+                           rotary_cos_table=None, rotary_sin_table=None, softmax_scale=None, kv_layout="blmhd",
+                           block_table=None, num_heads_kv=None, k_scale=None, v_scale=None):
+    """flash_decode_chunk over an fp8 KV cache (include/star_flash_attn.h, sfa_decode_chunk_kv8): the result of n
+    successive flash_decode_kv8 calls.  The caches are torch.uint8 or torch.float8_e4m3fn tensors, k_scale / v_scale
+    float32 device tensors [num_heads_kv] or None = 1.0, as in flash_decode_kv8; every other argument as in
+    flash_decode_chunk.  Token t is stored at row seq_len[b] + t as q8(x / scale) and attends to the rows
+    [0, seq_len[b] + t] of the cache after the append, the new rows through their stored values.  Returns `o`."""
+    lib = _lib.load()
+    _require(isinstance(qkv, torch.Tensor) and qkv.dim() in (4, 5),
+             f"qkv must be [B, n, 3, H, D] or [B, n, H + 2*Hkv, D] (got {tuple(getattr(qkv, 'shape', ()))})")
+    n = int(qkv.shape[1])
+    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
+                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
+                                      kv_layout, block_table, num_heads_kv, tokens=n, kv8=True)
+    dev = qkv.device
+    ks, vs = _kv8_scale(k_scale, "k_scale", Hkv, dev), _kv8_scale(v_scale, "v_scale", Hkv, dev)
+    with torch.cuda.device(dev):
+        S = int(num_splits) if num_splits and num_splits > 0 else 0
+        ws = _workspace(dev, lib.sfa_decode_chunk_workspace_bytes(B, H, Hkv, D, M, n, S))
+        _call_decode(dev, a, 0, S, ws, lambda args, stream: lib.sfa_decode_chunk_kv8(args, ks, vs, n, 0, stream))
+    return o
+
+
+def flash_decode_varlen_kv8(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, cu_tokens,
+                            batch_size, memory_max_len, num_heads, head_dim, rotary_embedding_dim,
+                            max_input_length, num_layer, idx_layer, *, num_splits=0,
+                            rotary_cos_table=None, rotary_sin_table=None, softmax_scale=None, kv_layout="blmhd",
+                            block_table=None, num_heads_kv=None, k_scale=None, v_scale=None):
+    """flash_decode_varlen over an fp8 KV cache (include/star_flash_attn.h, sfa_decode_varlen_kv8): every packed token
+    gets what flash_decode_chunk_kv8 gives it at pos = seq_len[b].  The caches and the scales as in flash_decode_kv8,
+    every other argument as in flash_decode_varlen.  Returns `o`."""
+    lib = _lib.load()
+    _require(isinstance(qkv, torch.Tensor) and qkv.dim() in (3, 4),
+             f"qkv must be [T, 3, H, D] or [T, H + 2*Hkv, D] (got {tuple(getattr(qkv, 'shape', ()))})")
+    T = int(qkv.shape[0])
+    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
+                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
+                                      kv_layout, block_table, num_heads_kv, packed=T, kv8=True)
+    dev = qkv.device
+    ks, vs = _kv8_scale(k_scale, "k_scale", Hkv, dev), _kv8_scale(v_scale, "v_scale", Hkv, dev)
+    _check_gpu_tensor(cu_tokens, "cu_tokens", torch.int32, (B + 1,), dev)
+    with torch.cuda.device(dev):
+        S = int(num_splits) if num_splits and num_splits > 0 else 0
+        ws = _workspace(dev, lib.sfa_decode_varlen_workspace_bytes(B, H, Hkv, D, M, T, S))
+        cu = ctypes.c_void_p(cu_tokens.data_ptr())
+        _call_decode(dev, a, 0, S, ws, lambda args, stream: lib.sfa_decode_varlen_kv8(args, ks, vs, cu, T, 0, stream))
     return o
 
 
