@@ -26,6 +26,7 @@
  *   sfa_decode_chunk_window     <- (no reference function: sfa_decode_chunk / sfa_decode_varlen with that window)
  *   sfa_decode_kv8_window       <- (no reference function: sfa_decode_kv8 over the last `window` positions)
  *   sfa_decode_chunk_kv8        <- (no reference function: sfa_decode_chunk / sfa_decode_varlen over an fp8 KV cache)
+ *   sfa_decode_chunk_kv8_window <- (no reference function: those two calls with the sliding window)
  * The Python-facing mha_fwd_cuda (src/flash_api.cpp:42-68) and the C++ template
  * surface (src/flash_attn.h) in this repo are thin layers over these symbols.
  */
@@ -54,7 +55,9 @@ extern "C" {
  *      multi-token calls) added under the same version, in the same way
  *      sfa_decode_kv8_window (the sliding window over an fp8 KV cache) added under the same version, in the same way
  *      sfa_decode_chunk_kv8 and sfa_decode_varlen_kv8 (the multi-token calls over an fp8 KV cache) added under the same
- *      version, in the same way; they have no sizing functions of their own */
+ *      version, in the same way; they have no sizing functions of their own
+ *      sfa_decode_chunk_kv8_window and sfa_decode_varlen_kv8_window (the sliding window in the multi-token calls over an
+ *      fp8 KV cache) added under the same version, in the same way; no sizing functions of their own either */
 #define SFA_ABI_VERSION 4
 
 typedef enum sfa_status {
@@ -345,9 +348,8 @@ size_t sfa_decode_window_workspace_bytes(int batch_size, int num_heads, int num_
  * sfa_decode_chunk_workspace_bytes / sfa_decode_varlen_workspace_bytes is never too small; one that holds fewer splits
  * than the library would pick gets the largest count it holds.  The split key range is the tiles that hold
  * [lo_0, pos + n), not [0, pos + n): a short window over a long history is shared by all splits.
- * Not served: an fp8 cache in these windowed multi-token calls (sfa_decode_kv8_window serves one token per sequence,
- * sfa_decode_chunk_kv8 / sfa_decode_varlen_kv8 the whole history), head_dim 256, ring-buffer caches, attention sinks,
- * soft-capping.
+ * Not served: head_dim 256, ring-buffer caches, attention sinks, soft-capping.  (An fp8 cache:
+ * sfa_decode_chunk_kv8_window / sfa_decode_varlen_kv8_window, below.)
  */
 int    sfa_decode_chunk_window(const sfa_decode_args *args, int num_tokens, int64_t qkv_token_stride, int window,
                                void *stream);
@@ -385,9 +387,8 @@ size_t sfa_decode_varlen_window_workspace_bytes(int batch_size, int num_heads, i
  * sfa_decode_window_workspace_bytes sizes it.  A workspace sized by sfa_decode_workspace_bytes_gqa is never too small;
  * with num_splits <= 0 one that holds fewer splits than the library would pick gets the largest count it holds.  The
  * same workspace and status word serve every decode entry point on a stream.
- * Not served: a sliding window over the fp8 cache in the multi-token calls (sfa_decode_chunk_kv8 / sfa_decode_varlen_kv8
- * attend to the whole history), head_dim 256, per-token or per-block scales, ring-buffer caches, attention sinks,
- * soft-capping.
+ * Not served: head_dim 256, per-token or per-block scales, ring-buffer caches, attention sinks, soft-capping.  (More
+ * than one token per sequence: sfa_decode_chunk_kv8_window / sfa_decode_varlen_kv8_window, below.)
  */
 int sfa_decode_kv8_window(const sfa_decode_args *args, const float *k_scale, const float *v_scale, int window,
                           void *stream);
@@ -418,13 +419,55 @@ int sfa_decode_kv8_window(const sfa_decode_args *args, const float *k_scale, con
  * sfa_decode_chunk / sfa_decode_varlen, and sfa_decode_chunk_workspace_bytes / sfa_decode_varlen_workspace_bytes size
  * it.  (The split rule was tuned on 16-bit rows and has not been re-tuned for one-byte rows.)  The same workspace and
  * status word serve every decode entry point on a stream.
- * Not served: a sliding window over the fp8 cache in these calls, head_dim 256, per-token or per-block scales, fp8
- * matrix instructions on a quantised Q.
+ * Not served: head_dim 256, per-token or per-block scales, fp8 matrix instructions on a quantised Q.  (A sliding
+ * window: sfa_decode_chunk_kv8_window / sfa_decode_varlen_kv8_window, below.)
  */
 int sfa_decode_chunk_kv8(const sfa_decode_args *args, const float *k_scale, const float *v_scale, int num_tokens,
                          int64_t qkv_token_stride, void *stream);
 int sfa_decode_varlen_kv8(const sfa_decode_args *args, const float *k_scale, const float *v_scale,
                           const void *cu_tokens, int total_tokens, int64_t qkv_token_stride, void *stream);
+
+/* ---- multi-token decode with a sliding window over an fp8 KV cache ----------------- */
+/*
+ * sfa_decode_chunk_kv8 / sfa_decode_varlen_kv8 for a sliding-window attention layer: the call gives exactly what n
+ * successive sfa_decode_kv8_window calls would.  It is the conjunction of the contracts of sfa_decode_chunk_kv8 /
+ * sfa_decode_varlen_kv8 and of sfa_decode_chunk_window / sfa_decode_varlen_window.
+ * Everything of sfa_decode_chunk_kv8 / sfa_decode_varlen_kv8 holds unchanged: the qkv / o shapes and strides, bias, RoPE
+ * at pos + t, the rotary tables, partial rotary, the three kv_layouts of e4m3 bytes (strides in elements = bytes, 16-byte
+ * aligned), num_heads / num_heads_kv in {1, 2, 4, 8, 16}, fp16 / bf16, head_dim 64 / 128 (256 returns
+ * SFA_ERR_UNSUPPORTED_HEAD_DIM); k_scale / v_scale are device fp32 [num_heads_kv], 4-byte aligned (checked: otherwise
+ * SFA_ERR_BAD_SHAPE), finite and > 0 (not checked), NULL = 1.0; row pos + t receives k8 = q8(k16 / k_scale[hk]),
+ * v8 = q8(v16 / v_scale[hk]) and no other byte of a cache changes; the cu_tokens rules and n_b == 0, the rejection rules
+ * and the status word; seq_len is not incremented; the call allocates nothing, never synchronises and may be captured in
+ * a graph and replayed with other seq_len / cu_tokens contents.
+ * The only difference is the key range.  Token t of a sequence at pos = seq_len[b] attends to the rows [lo_t, pos + t] of
+ * the cache AFTER the append, with lo_t = max(0, pos + t + 1 - window):
+ *   o = softmax(q16 . (k_scale[hk] * K8[lo_t..pos+t])^T * head_dim_inv) . (v_scale[hk] * V8[lo_t..pos+t])  (fp32 accumulate)
+ * The new rows, its own included, enter through their stored bytes.
+ *   window >= 1     window < 1 returns SFA_ERR_BAD_SHAPE.  window = 1 leaves each token its own quantised row only; when
+ *                   window >= pos + n for every sequence the call is sfa_decode_chunk_kv8 / sfa_decode_varlen_kv8, bit
+ *                   for bit, at the same explicit num_splits.
+ * What the window promises is what sfa_decode_chunk_window promises, with lo_0 = max(0, pos + 1 - window) and n the
+ * sequence's token count; the cache being bytes, "anything" includes the NaN byte 0x7F:
+ *   - cache rows below lo_0, rows from pos + n on and the other layers are never read and may hold anything;
+ *   - in a paged cache the block_table entries [0, lo_0 / page_size) are never read and may hold any value, -1 included;
+ *   - only a bad entry on a page that intersects [lo_0, pos + n) raises SFA_ERR_BLOCK_TABLE_RANGE: on a page that covers
+ *     new rows it rejects the sequence, on a page that is only read it makes the affected outputs NaN.
+ * Workspace: there are no sizing functions of their own.  Layout, split rule and status word are those of
+ * sfa_decode_chunk_window / sfa_decode_varlen_window: with num_splits <= 0 the chunk / varlen rule over
+ * min(memory_max_len, window - 1 + count) rows, a workspace that holds fewer splits than that gets the largest count it
+ * holds, and the split key range is the tiles that hold [lo_0, pos + n).  sfa_decode_chunk_window_workspace_bytes /
+ * sfa_decode_varlen_window_workspace_bytes size it; a workspace sized by sfa_decode_chunk_workspace_bytes /
+ * sfa_decode_varlen_workspace_bytes is never too small.  The same workspace and status word serve every decode entry
+ * point on a stream.
+ * Not served: head_dim 256, per-token or per-block scales, ring-buffer caches, attention sinks, soft-capping, fp8 matrix
+ * instructions on a quantised Q.
+ */
+int sfa_decode_chunk_kv8_window(const sfa_decode_args *args, const float *k_scale, const float *v_scale, int num_tokens,
+                                int64_t qkv_token_stride, int window, void *stream);
+int sfa_decode_varlen_kv8_window(const sfa_decode_args *args, const float *k_scale, const float *v_scale,
+                                 const void *cu_tokens, int total_tokens, int64_t qkv_token_stride, int window,
+                                 void *stream);
 
 /* ---- prefill: O = softmax(mask(Q K^T * scale)) V ------------------------------- */
 /*

@@ -148,6 +148,8 @@ constexpr EntryPoint kChunkWindow = {"sfa_decode_chunk_window", "num_tokens", fa
 constexpr EntryPoint kVarlenWindow = {"sfa_decode_varlen_window", "total_tokens", false, true, true};
 constexpr EntryPoint kChunkKv8 = {"sfa_decode_chunk_kv8", "num_tokens", false, true, false};
 constexpr EntryPoint kVarlenKv8 = {"sfa_decode_varlen_kv8", "total_tokens", false, true, true};
+constexpr EntryPoint kChunkKv8Window = {"sfa_decode_chunk_kv8_window", "num_tokens", false, true, false};
+constexpr EntryPoint kVarlenKv8Window = {"sfa_decode_varlen_kv8_window", "total_tokens", false, true, true};
 
 // What the entry points check alike, before any HIP call, and what they derive on the way.  sfa_decode is the case of
 // one token per sequence (count = 1) with no token stride.
@@ -695,6 +697,55 @@ int sfa_decode_varlen_kv8(const sfa_decode_args *a, const float *k_scale, const 
     p.k_scale = k_scale;
     p.v_scale = v_scale;
     return launch_decode_varlen_kv8(p, a->dtype, a->head_dim, (hipStream_t)stream);
+}
+
+// sfa_decode_chunk_kv8 with a sliding window: the checks of sfa_decode_chunk_kv8 and sfa_decode_chunk_window, in the fp8
+// twin's order (scales before the workspace); the workspace, its split rule and the status word are
+// sfa_decode_chunk_window's
+int sfa_decode_chunk_kv8_window(const sfa_decode_args *a, const float *k_scale, const float *v_scale, int num_tokens,
+                                int64_t qkv_token_stride, int window, void *stream) {
+    DecodeCall dc;
+    if (const int rc = validate_decode_call(kChunkKv8Window, a, num_tokens, qkv_token_stride, &dc)) return rc;
+    if (((uintptr_t)k_scale | (uintptr_t)v_scale) & 3)
+        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk_kv8_window: k_scale / v_scale must be 4-byte aligned");
+    if (window < 1) return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk_kv8_window: window=%d must be >= 1", window);
+    if (a->batch_size == 0 || num_tokens == 0) return SFA_OK;
+
+    const int rows = num_tokens * dc.group;
+    int S = a->num_splits > 0 ? a->num_splits
+                              : chunk_auto_splits(a->batch_size, dc.hkv, rows, window_rows(a->memory_max_len, window, num_tokens));
+    // as in sfa_decode_chunk_window: a workspace sized for fewer splits than the library would pick gets the largest count
+    // it holds
+    if (a->num_splits <= 0 && a->workspace)
+        while (S > 1 && a->workspace_bytes < chunk_workspace(a->batch_size, dc.hkv, rows, S, a->head_dim).total) --S;
+    const DecodeWorkspace w = chunk_workspace(a->batch_size, dc.hkv, rows, S, a->head_dim);
+    if (const int rc = check_workspace(kChunkKv8Window, a, w.total)) return rc;
+
+    ChunkKv8WindowKernelParams p;
+    memset(&p, 0, sizeof(p));
+    p.base = chunk_params(a, dc, num_tokens, S, w);
+    p.window = window;
+    p.k_scale = k_scale;
+    p.v_scale = v_scale;
+    return launch_decode_chunk_kv8_window(p, a->dtype, a->head_dim, (hipStream_t)stream);
+}
+
+// sfa_decode_varlen_kv8 with a sliding window: as sfa_decode_chunk_kv8_window is to sfa_decode_chunk_kv8
+int sfa_decode_varlen_kv8_window(const sfa_decode_args *a, const float *k_scale, const float *v_scale,
+                                 const void *cu_tokens, int total_tokens, int64_t qkv_token_stride, int window,
+                                 void *stream) {
+    VarlenKv8WindowKernelParams p;
+    memset(&p, 0, sizeof(p));
+    // (before varlen_call, whose last check is the workspace: as in sfa_decode_varlen_kv8)
+    if (((uintptr_t)k_scale | (uintptr_t)v_scale) & 3)
+        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_varlen_kv8_window: k_scale / v_scale must be 4-byte aligned");
+    if (const int rc = varlen_call(kVarlenKv8Window, a, cu_tokens, total_tokens, qkv_token_stride, true, window, &p.base))
+        return rc;
+    if (!p.base.cu_tokens) return SFA_OK;       // nothing to do
+    p.window = window;
+    p.k_scale = k_scale;
+    p.v_scale = v_scale;
+    return launch_decode_varlen_kv8_window(p, a->dtype, a->head_dim, (hipStream_t)stream);
 }
 
 int sfa_prefill_fwd(const sfa_prefill_args *a, void *stream) {

@@ -26,6 +26,9 @@
 // bytes, the attention kernel stages bytes and converts them on their way into the same 16-bit LDS tiles, and the scales
 // go into the score scale and the epilogue; the combine kernel does not look at the flag.  Without it none of the fp8
 // code is compiled.
+//
+// The two properties are independent in the kernels, and Kv8WindowGeo<BASE, P> carries both
+// (sfa_decode_chunk_kv8_window / sfa_decode_varlen_kv8_window).
 #pragma once
 #include "decode_chunk_common.h"
 #include "kv8_convert.h"
@@ -86,6 +89,18 @@ struct WindowGeo : ForwardGeo<BASE, P> {
 template <class BASE, class P>
 struct Kv8Geo : ForwardGeo<BASE, P> {
     static constexpr bool kKv8 = true;
+    static __device__ __forceinline__ const float *k_scale(const P &gp) { return gp.k_scale; }
+    static __device__ __forceinline__ const float *v_scale(const P &gp) { return gp.v_scale; }
+};
+
+// BASE with both: P holds BASE's Params as `base`, `window`, `k_scale` and `v_scale`.  One wrapper rather than one of the
+// two above around the other: each of them forwards to ForwardGeo, so the outer one would hide the inner one's flag and
+// accessors
+template <class BASE, class P>
+struct Kv8WindowGeo : ForwardGeo<BASE, P> {
+    static constexpr bool kWindow = true;
+    static constexpr bool kKv8 = true;
+    static __device__ __forceinline__ int window(const P &gp) { return gp.window; }
     static __device__ __forceinline__ const float *k_scale(const P &gp) { return gp.k_scale; }
     static __device__ __forceinline__ const float *v_scale(const P &gp) { return gp.v_scale; }
 };

@@ -1,0 +1,25 @@
+// sfa_decode_varlen_kv8_window for gfx950 (MI355X): sfa_decode_varlen_kv8 (decode_varlen_kv8_kernel.hip) with a sliding
+// window -- each token gets exactly what sfa_decode_chunk_kv8_window gives it at pos = seq_len[b].  The plan kernel, the
+// four launches, the grids and the workspace are the ragged call's; the kernels are decode_chunk_body.h's under the
+// ragged geometry with both flags (decode_chunk_kv8_window_kernel.hip).
+#include "decode_varlen_geo.h"
+
+namespace sfa {
+
+namespace {
+
+using RaggedKv8WindowGeo = chunk::Kv8WindowGeo<RaggedGeo, VarlenKv8WindowKernelParams>;
+
+}  // namespace
+
+int launch_decode_varlen_kv8_window(const VarlenKv8WindowKernelParams &kp, int dtype, int head_dim, hipStream_t stream) {
+    const VarlenKernelParams &vp = kp.base;
+    const DecodeKernelParams &p = vp.c.d;
+    hipLaunchKernelGGL(varlen_plan_kernel, dim3(1), dim3(256), 0, stream, vp);
+    if (const int rc = check_launch("varlen_plan_kernel")) return rc;
+    return chunk::launch_chunk<RaggedKv8WindowGeo>(kp, p, dtype, head_dim, dim3(vp.total),
+                                                   dim3((unsigned)vp.bound * (unsigned)(p.Hkv * p.num_splits)),
+                                                   (long long)p.Hkv * vp.rows, stream);
+}
+
+}  // namespace sfa

@@ -103,6 +103,20 @@ struct VarlenKv8KernelParams {
     const float *k_scale, *v_scale;
 };
 
+// sfa_decode_chunk_kv8_window / sfa_decode_varlen_kv8_window (decode_chunk_kv8_window_kernel.hip,
+// decode_varlen_kv8_window_kernel.hip): the chunk and varlen calls over e4m3 caches with a sliding window -- the window
+// and the scales of the structs above, with their meanings, behind the same unchanged parameters.
+struct ChunkKv8WindowKernelParams {
+    ChunkKernelParams base;
+    int window;
+    const float *k_scale, *v_scale;
+};
+struct VarlenKv8WindowKernelParams {
+    VarlenKernelParams base;
+    int window;
+    const float *k_scale, *v_scale;
+};
+
 // sfa_decode_window (decode_window_kernel.hip, the body of decode_mfma16.h with its window): sfa_decode over the last
 // `window` positions.
 struct WindowKernelParams {
@@ -146,6 +160,8 @@ int launch_decode_chunk_window(const ChunkWindowKernelParams &p, int dtype, int 
 int launch_decode_varlen_window(const VarlenWindowKernelParams &p, int dtype, int head_dim, hipStream_t stream);
 int launch_decode_chunk_kv8(const ChunkKv8KernelParams &p, int dtype, int head_dim, hipStream_t stream);
 int launch_decode_varlen_kv8(const VarlenKv8KernelParams &p, int dtype, int head_dim, hipStream_t stream);
+int launch_decode_chunk_kv8_window(const ChunkKv8WindowKernelParams &p, int dtype, int head_dim, hipStream_t stream);
+int launch_decode_varlen_kv8_window(const VarlenKv8WindowKernelParams &p, int dtype, int head_dim, hipStream_t stream);
 // decode_kv8_kernel.hip: the attention kernel over e4m3 caches plus the split combine; the 16-bit -> e4m3 row copy
 int launch_decode_kv8(const Kv8KernelParams &p, int dtype, int head_dim, hipStream_t stream);
 int launch_kv8_quantize(void *dst, const void *src, const float *scale, long long rows, int Hkv, int head_dim,

@@ -19,6 +19,9 @@ libStarFlashAttention.so.  The public operators:
                       window: what n successive flash_decode_window calls give (new entry points).
   flash_decode_chunk_kv8(...) / flash_decode_varlen_kv8(...)  flash_decode_chunk / flash_decode_varlen over an fp8 KV
                       cache: what n successive flash_decode_kv8 calls give (new entry points).
+  flash_decode_chunk_kv8_window(...)  flash_decode_chunk_kv8 with the sliding window: what n successive
+                      flash_decode_kv8_window calls give (new entry point).
+  flash_decode_varlen_kv8_window(...)  flash_decode_varlen_kv8 with the sliding window (new entry point).
 """
 import ctypes
 import math
@@ -472,6 +475,65 @@ def flash_decode_varlen_window(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cac
         ws = _workspace(dev, lib.sfa_decode_varlen_window_workspace_bytes(B, H, Hkv, D, M, T, W, S))
         cu = ctypes.c_void_p(cu_tokens.data_ptr())
         _call_decode(dev, a, 0, S, ws, lambda args, stream: lib.sfa_decode_varlen_window(args, cu, T, 0, W, stream))
+    return o
+
+
+def flash_decode_chunk_kv8_window(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o,
+                                  batch_size, memory_max_len, num_heads, head_dim, rotary_embedding_dim,
+                                  max_input_length, num_layer, idx_layer, window, *, num_splits=0,
+                                  rotary_cos_table=None, rotary_sin_table=None, softmax_scale=None, kv_layout="blmhd",
+                                  block_table=None, num_heads_kv=None, k_scale=None, v_scale=None):
+    """flash_decode_chunk_kv8 with a sliding window (include/star_flash_attn.h, sfa_decode_chunk_kv8_window): the result
+    of n successive flash_decode_kv8_window calls.  Token t is stored at row seq_len[b] + t as q8(x / scale) and attends
+    to the rows [max(0, seq_len[b] + t + 1 - window), seq_len[b] + t] of the cache after the append, the new rows through
+    their stored values.  window >= 1; the caches and the scales as in flash_decode_kv8, every other argument as in
+    flash_decode_chunk.  Cache rows below lo_0 = max(0, seq_len[b] + 1 - window), and block_table entries of pages wholly
+    below lo_0, are never read.  Returns `o`."""
+    lib = _lib.load()
+    _require(isinstance(qkv, torch.Tensor) and qkv.dim() in (4, 5),
+             f"qkv must be [B, n, 3, H, D] or [B, n, H + 2*Hkv, D] (got {tuple(getattr(qkv, 'shape', ()))})")
+    n = int(qkv.shape[1])
+    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
+                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
+                                      kv_layout, block_table, num_heads_kv, tokens=n, kv8=True)
+    W = _window_int(window)
+    dev = qkv.device
+    ks, vs = _kv8_scale(k_scale, "k_scale", Hkv, dev), _kv8_scale(v_scale, "v_scale", Hkv, dev)
+    with torch.cuda.device(dev):
+        S = int(num_splits) if num_splits and num_splits > 0 else 0
+        ws = _workspace(dev, lib.sfa_decode_chunk_window_workspace_bytes(B, H, Hkv, D, M, n, W, S))
+        _call_decode(dev, a, 0, S, ws,
+                     lambda args, stream: lib.sfa_decode_chunk_kv8_window(args, ks, vs, n, 0, W, stream))
+    return o
+
+
+def flash_decode_varlen_kv8_window(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, cu_tokens,
+                                   batch_size, memory_max_len, num_heads, head_dim, rotary_embedding_dim,
+                                   max_input_length, num_layer, idx_layer, window, *, num_splits=0,
+                                   rotary_cos_table=None, rotary_sin_table=None, softmax_scale=None, kv_layout="blmhd",
+                                   block_table=None, num_heads_kv=None, k_scale=None, v_scale=None):
+    """flash_decode_varlen_kv8 with a sliding window (include/star_flash_attn.h, sfa_decode_varlen_kv8_window): every
+    packed token gets what flash_decode_chunk_kv8_window gives it at pos = seq_len[b].  window >= 1; the caches and the
+    scales as in flash_decode_kv8, every other argument as in flash_decode_varlen.  Returns `o`."""
+    lib = _lib.load()
+    _require(isinstance(qkv, torch.Tensor) and qkv.dim() in (3, 4),
+             f"qkv must be [T, 3, H, D] or [T, H + 2*Hkv, D] (got {tuple(getattr(qkv, 'shape', ()))})")
+    T = int(qkv.shape[0])
+    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
+                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
+                                      kv_layout, block_table, num_heads_kv, packed=T, kv8=True)
+    W = _window_int(window)
+    dev = qkv.device
+    ks, vs = _kv8_scale(k_scale, "k_scale", Hkv, dev), _kv8_scale(v_scale, "v_scale", Hkv, dev)
+    _check_gpu_tensor(cu_tokens, "cu_tokens", torch.int32, (B + 1,), dev)
+    with torch.cuda.device(dev):
+        S = int(num_splits) if num_splits and num_splits > 0 else 0
+        ws = _workspace(dev, lib.sfa_decode_varlen_window_workspace_bytes(B, H, Hkv, D, M, T, W, S))
+        cu = ctypes.c_void_p(cu_tokens.data_ptr())
+        _call_decode(dev, a, 0, S, ws,
+                     lambda args, stream: lib.sfa_decode_varlen_kv8_window(args, ks, vs, cu, T, 0, W, stream))
     return o
 
 
