@@ -57,7 +57,10 @@ extern "C" {
  *      sfa_decode_chunk_kv8 and sfa_decode_varlen_kv8 (the multi-token calls over an fp8 KV cache) added under the same
  *      version, in the same way; they have no sizing functions of their own
  *      sfa_decode_chunk_kv8_window and sfa_decode_varlen_kv8_window (the sliding window in the multi-token calls over an
- *      fp8 KV cache) added under the same version, in the same way; no sizing functions of their own either */
+ *      fp8 KV cache) added under the same version, in the same way; no sizing functions of their own either
+ *      sfa_decode_window_sinks, sfa_decode_chunk_window_sinks and sfa_decode_varlen_window_sinks (attention sinks in the
+ *      three windowed calls over 16-bit caches) added under the same version, in the same way; no sizing functions of
+ *      their own either */
 #define SFA_ABI_VERSION 4
 
 typedef enum sfa_status {
@@ -348,8 +351,9 @@ size_t sfa_decode_window_workspace_bytes(int batch_size, int num_heads, int num_
  * sfa_decode_chunk_workspace_bytes / sfa_decode_varlen_workspace_bytes is never too small; one that holds fewer splits
  * than the library would pick gets the largest count it holds.  The split key range is the tiles that hold
  * [lo_0, pos + n), not [0, pos + n): a short window over a long history is shared by all splits.
- * Not served: head_dim 256, ring-buffer caches, attention sinks, soft-capping.  (An fp8 cache:
- * sfa_decode_chunk_kv8_window / sfa_decode_varlen_kv8_window, below.)
+ * Not served: head_dim 256, ring-buffer caches, soft-capping.  (An fp8 cache: sfa_decode_chunk_kv8_window /
+ * sfa_decode_varlen_kv8_window, below.  Attention sinks: sfa_decode_window_sinks / sfa_decode_chunk_window_sinks /
+ * sfa_decode_varlen_window_sinks, below, for these two calls and for sfa_decode_window.)
  */
 int    sfa_decode_chunk_window(const sfa_decode_args *args, int num_tokens, int64_t qkv_token_stride, int window,
                                void *stream);
@@ -359,6 +363,41 @@ int    sfa_decode_varlen_window(const sfa_decode_args *args, const void *cu_toke
                                 int64_t qkv_token_stride, int window, void *stream);
 size_t sfa_decode_varlen_window_workspace_bytes(int batch_size, int num_heads, int num_heads_kv, int head_dim,
                                                 int memory_max_len, int total_tokens, int window, int num_splits);
+
+/* ---- sliding-window decode with attention sinks ------------------------------------ */
+/*
+ * sfa_decode_window / sfa_decode_chunk_window / sfa_decode_varlen_window for a layer whose softmax carries a learned
+ * per-head sink logit (gpt-oss: 64 query heads over 8 kv heads, head_dim 64, a 128-row window on every second layer).
+ * Everything of the _window call each one extends holds unchanged: bias, RoPE, the append, the three kv_layouts,
+ * num_heads / num_heads_kv in {1, 2, 4, 8, 16}, fp16 / bf16, head_dim 64 / 128 / 256 for the single-token call and
+ * 64 / 128 for the other two (256 returns SFA_ERR_UNSUPPORTED_HEAD_DIM), the never-read promises below lo / lo_0, the
+ * cu_tokens rules, the rejection rules and the status bits; the call allocates nothing, never synchronises and may be
+ * captured in a graph.  A layer with full attention passes window >= memory_max_len (INT_MAX works); window < 1 returns
+ * SFA_ERR_BAD_SHAPE.
+ *   sinks           device fp32 [num_heads], one logit per QUERY head, 4-byte aligned (checked: otherwise
+ *                   SFA_ERR_BAD_SHAPE).  Every value is finite or -inf (the caller's contract, not checked).  Read on
+ *                   the device only: a replayed graph sees new contents.
+ *                   NULL: the call validates under its own name and then launches exactly what the _window call
+ *                   launches; output and caches are bit-identical to it.
+ * Semantics, for query head h over its key range [lo, pos] (chunk / varlen: [lo_t, pos + t]), s_j = q . K_j * head_dim_inv:
+ *   o[h] = sum_j exp(s_j) V_j / (exp(sinks[h]) + sum_j exp(s_j))
+ * -- one more key with logit sinks[h] and a zero value row.  The sink is NOT multiplied by head_dim_inv.  The output is
+ * a function of the sink and the cache after the call; the caches receive exactly what the _window call stores.
+ * Numerics: the sink joins the online softmax once per query row, whatever the split count.  A sink far above the scores
+ * gives a small finite output, with no overflow; a sink whose weight underflows in fp32 (-inf is one) gives the _window
+ * call's output bit for bit at the same explicit num_splits.
+ * Workspace: there are no sizing functions of their own.  Layout, split rule and status word are those of the _window
+ * call each one extends, and sfa_decode_window_workspace_bytes / sfa_decode_chunk_window_workspace_bytes /
+ * sfa_decode_varlen_window_workspace_bytes size it; with num_splits <= 0 a workspace that holds fewer splits than the
+ * library would pick gets the largest count it holds.
+ * Not served: sinks over an fp8 cache (the _kv8 calls do not serve sinks yet), head_dim 256 in the multi-token calls,
+ * ring-buffer caches, soft-capping.
+ */
+int sfa_decode_window_sinks(const sfa_decode_args *args, const float *sinks, int window, void *stream);
+int sfa_decode_chunk_window_sinks(const sfa_decode_args *args, const float *sinks, int num_tokens,
+                                  int64_t qkv_token_stride, int window, void *stream);
+int sfa_decode_varlen_window_sinks(const sfa_decode_args *args, const float *sinks, const void *cu_tokens,
+                                   int total_tokens, int64_t qkv_token_stride, int window, void *stream);
 
 /* ---- decode with a sliding window over an fp8 KV cache ------------------------------ */
 /*
@@ -387,7 +426,8 @@ size_t sfa_decode_varlen_window_workspace_bytes(int batch_size, int num_heads, i
  * sfa_decode_window_workspace_bytes sizes it.  A workspace sized by sfa_decode_workspace_bytes_gqa is never too small;
  * with num_splits <= 0 one that holds fewer splits than the library would pick gets the largest count it holds.  The
  * same workspace and status word serve every decode entry point on a stream.
- * Not served: head_dim 256, per-token or per-block scales, ring-buffer caches, attention sinks, soft-capping.  (More
+ * Not served: head_dim 256, per-token or per-block scales, ring-buffer caches, attention sinks (the _sinks calls serve
+ * 16-bit caches only; the fp8 calls do not serve sinks yet), soft-capping.  (More
  * than one token per sequence: sfa_decode_chunk_kv8_window / sfa_decode_varlen_kv8_window, below.)
  */
 int sfa_decode_kv8_window(const sfa_decode_args *args, const float *k_scale, const float *v_scale, int window,
@@ -460,8 +500,8 @@ int sfa_decode_varlen_kv8(const sfa_decode_args *args, const float *k_scale, con
  * sfa_decode_varlen_window_workspace_bytes size it; a workspace sized by sfa_decode_chunk_workspace_bytes /
  * sfa_decode_varlen_workspace_bytes is never too small.  The same workspace and status word serve every decode entry
  * point on a stream.
- * Not served: head_dim 256, per-token or per-block scales, ring-buffer caches, attention sinks, soft-capping, fp8 matrix
- * instructions on a quantised Q.
+ * Not served: head_dim 256, per-token or per-block scales, ring-buffer caches, attention sinks (the _sinks calls serve
+ * 16-bit caches only; the fp8 calls do not serve sinks yet), soft-capping, fp8 matrix instructions on a quantised Q.
  */
 int sfa_decode_chunk_kv8_window(const sfa_decode_args *args, const float *k_scale, const float *v_scale, int num_tokens,
                                 int64_t qkv_token_stride, int window, void *stream);

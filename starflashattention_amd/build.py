@@ -30,7 +30,9 @@ KERNEL_SOURCES = ["prefill_w4_kernel.hip", "prefill_w4_kernel_p1.hip", "prefill_
                   "prefill_w4d_kernel.hip", "decode_chunk_kernel.hip", "decode_varlen_kernel.hip",
                   "decode_chunk_window_kernel.hip", "decode_varlen_window_kernel.hip",
                   "decode_chunk_kv8_kernel.hip", "decode_varlen_kv8_kernel.hip",
-                  "decode_chunk_kv8_window_kernel.hip", "decode_varlen_kv8_window_kernel.hip", "decode_kernel.hip", "decode_gqa_kernel.hip", "decode_gqa_mfma_kernel.hip", "decode_kv8_kernel.hip", "decode_kv8_window_kernel.hip", "decode_window_kernel.hip",
+                  "decode_chunk_kv8_window_kernel.hip", "decode_varlen_kv8_window_kernel.hip",
+                  "decode_chunk_window_sinks_kernel.hip", "decode_varlen_window_sinks_kernel.hip",
+                  "decode_window_sinks_kernel.hip", "decode_kernel.hip", "decode_gqa_kernel.hip", "decode_gqa_mfma_kernel.hip", "decode_kv8_kernel.hip", "decode_kv8_window_kernel.hip", "decode_window_kernel.hip",
                   "prefill_d256_kernel.hip",
                   "prefill_kernel.hip", "prefill_kernel_bm128.hip", "prefill_dispatch.hip", "decode_dispatch.hip",
                   "aux_kernels.hip", "c_api.hip", "cxx_surface.hip"]

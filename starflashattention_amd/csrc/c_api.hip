@@ -146,6 +146,9 @@ constexpr EntryPoint kWindow = {"sfa_decode_window", "num_tokens", true, false, 
 constexpr EntryPoint kKv8Window = {"sfa_decode_kv8_window", "num_tokens", true, false, false};
 constexpr EntryPoint kChunkWindow = {"sfa_decode_chunk_window", "num_tokens", false, true, false};
 constexpr EntryPoint kVarlenWindow = {"sfa_decode_varlen_window", "total_tokens", false, true, true};
+constexpr EntryPoint kWindowSinks = {"sfa_decode_window_sinks", "num_tokens", true, false, false};
+constexpr EntryPoint kChunkWindowSinks = {"sfa_decode_chunk_window_sinks", "num_tokens", false, true, false};
+constexpr EntryPoint kVarlenWindowSinks = {"sfa_decode_varlen_window_sinks", "total_tokens", false, true, true};
 constexpr EntryPoint kChunkKv8 = {"sfa_decode_chunk_kv8", "num_tokens", false, true, false};
 constexpr EntryPoint kVarlenKv8 = {"sfa_decode_varlen_kv8", "total_tokens", false, true, true};
 constexpr EntryPoint kChunkKv8Window = {"sfa_decode_chunk_kv8_window", "num_tokens", false, true, false};
@@ -413,10 +416,13 @@ size_t sfa_decode_window_workspace_bytes(int batch_size, int num_heads, int num_
     return sfa_decode_workspace_bytes(batch_size, num_heads, head_dim, memory_max_len, S);
 }
 
-int sfa_decode_window(const sfa_decode_args *a, int window, void *stream) {
+// sfa_decode_window and its twin with attention sinks up to the launch: the checks, the split count, the workspace and
+// the kernel parameters.  *run = false: nothing to do
+static int window_call(const EntryPoint &e, const sfa_decode_args *a, int window, WindowKernelParams *out, bool *run) {
     DecodeCall dc;
-    if (const int rc = validate_decode_call(kWindow, a, 1, 0, &dc)) return rc;
-    if (window < 1) return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_window: window=%d must be >= 1", window);
+    *run = false;
+    if (const int rc = validate_decode_call(e, a, 1, 0, &dc)) return rc;
+    if (window < 1) return fail(SFA_ERR_BAD_SHAPE, "%s: window=%d must be >= 1", e.fn, window);
     if (a->batch_size == 0) return SFA_OK;
 
     const size_t bh = (size_t)a->batch_size * a->num_heads;
@@ -425,16 +431,38 @@ int sfa_decode_window(const sfa_decode_args *a, int window, void *stream) {
     if (a->num_splits <= 0 && a->workspace)
         while (S > 1 && a->workspace_bytes < decode_workspace(0, 0, bh, S, a->head_dim).total) --S;
     const DecodeWorkspace w = decode_workspace(0, 0, bh, S, a->head_dim);
-    if (const int rc = check_workspace(kWindow, a, w.total)) return rc;
+    if (const int rc = check_workspace(e, a, w.total)) return rc;
 
-    WindowKernelParams p;
-    memset(&p, 0, sizeof(p));
+    WindowKernelParams &p = *out;
     p.d = decode_params(a, dc.hkv, dc.page_shift, S, dc.stride);
     char *ws = (char *)a->workspace;
     p.d.part_o = (float *)(ws + w.part_o);
     p.d.part_ml = (float2 *)(ws + w.part_ml);
     p.window = window;
+    *run = true;
+    return SFA_OK;
+}
+
+int sfa_decode_window(const sfa_decode_args *a, int window, void *stream) {
+    WindowKernelParams p;
+    memset(&p, 0, sizeof(p));
+    bool run;
+    if (const int rc = window_call(kWindow, a, window, &p, &run)) return rc;
+    if (!run) return SFA_OK;
     return launch_decode_window(p, a->dtype, a->head_dim, (hipStream_t)stream);
+}
+
+// sfa_decode_window with an attention sink per query head.  sinks == NULL: the call is sfa_decode_window's, launch and all
+int sfa_decode_window_sinks(const sfa_decode_args *a, const float *sinks, int window, void *stream) {
+    WindowSinksKernelParams p;
+    memset(&p, 0, sizeof(p));
+    bool run;
+    if (a && ((uintptr_t)sinks & 3)) return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_window_sinks: sinks must be 4-byte aligned");
+    if (const int rc = window_call(kWindowSinks, a, window, &p.base, &run)) return rc;
+    if (!run) return SFA_OK;
+    if (!sinks) return launch_decode_window(p.base, a->dtype, a->head_dim, (hipStream_t)stream);
+    p.sinks = sinks;
+    return launch_decode_window_sinks(p, a->dtype, a->head_dim, (hipStream_t)stream);
 }
 
 // sfa_decode_kv8 with a sliding window: the checks of sfa_decode_kv8 and sfa_decode_window; the workspace, its split
@@ -554,11 +582,13 @@ size_t sfa_decode_chunk_window_workspace_bytes(int batch_size, int num_heads, in
                                             window_rows(memory_max_len, window, num_tokens), num_tokens, num_splits);
 }
 
-int sfa_decode_chunk_window(const sfa_decode_args *a, int num_tokens, int64_t qkv_token_stride, int window,
-                            void *stream) {
+// sfa_decode_chunk_window and its twin with attention sinks up to the launch.  *run = false: nothing to do
+static int chunk_window_call(const EntryPoint &e, const sfa_decode_args *a, int num_tokens, int64_t qkv_token_stride,
+                             int window, ChunkKernelParams *out, bool *run) {
     DecodeCall dc;
-    if (const int rc = validate_decode_call(kChunkWindow, a, num_tokens, qkv_token_stride, &dc)) return rc;
-    if (window < 1) return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk_window: window=%d must be >= 1", window);
+    *run = false;
+    if (const int rc = validate_decode_call(e, a, num_tokens, qkv_token_stride, &dc)) return rc;
+    if (window < 1) return fail(SFA_ERR_BAD_SHAPE, "%s: window=%d must be >= 1", e.fn, window);
     if (a->batch_size == 0 || num_tokens == 0) return SFA_OK;
 
     const int rows = num_tokens * dc.group;
@@ -568,13 +598,43 @@ int sfa_decode_chunk_window(const sfa_decode_args *a, int num_tokens, int64_t qk
     if (a->num_splits <= 0 && a->workspace)
         while (S > 1 && a->workspace_bytes < chunk_workspace(a->batch_size, dc.hkv, rows, S, a->head_dim).total) --S;
     const DecodeWorkspace w = chunk_workspace(a->batch_size, dc.hkv, rows, S, a->head_dim);
-    if (const int rc = check_workspace(kChunkWindow, a, w.total)) return rc;
+    if (const int rc = check_workspace(e, a, w.total)) return rc;
+    *out = chunk_params(a, dc, num_tokens, S, w);
+    *run = true;
+    return SFA_OK;
+}
 
+int sfa_decode_chunk_window(const sfa_decode_args *a, int num_tokens, int64_t qkv_token_stride, int window,
+                            void *stream) {
     ChunkWindowKernelParams p;
     memset(&p, 0, sizeof(p));
-    p.base = chunk_params(a, dc, num_tokens, S, w);
+    bool run;
+    if (const int rc = chunk_window_call(kChunkWindow, a, num_tokens, qkv_token_stride, window, &p.base, &run)) return rc;
+    if (!run) return SFA_OK;
     p.window = window;
     return launch_decode_chunk_window(p, a->dtype, a->head_dim, (hipStream_t)stream);
+}
+
+// sfa_decode_chunk_window with an attention sink per query head.  sinks == NULL: the call is sfa_decode_chunk_window's
+int sfa_decode_chunk_window_sinks(const sfa_decode_args *a, const float *sinks, int num_tokens, int64_t qkv_token_stride,
+                                  int window, void *stream) {
+    ChunkWindowSinksKernelParams p;
+    memset(&p, 0, sizeof(p));
+    bool run;
+    if (a && ((uintptr_t)sinks & 3)) return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk_window_sinks: sinks must be 4-byte aligned");
+    if (const int rc = chunk_window_call(kChunkWindowSinks, a, num_tokens, qkv_token_stride, window, &p.base, &run))
+        return rc;
+    if (!run) return SFA_OK;
+    p.window = window;
+    p.sinks = sinks;
+    if (!sinks) {
+        ChunkWindowKernelParams wp;
+        memset(&wp, 0, sizeof(wp));
+        wp.base = p.base;
+        wp.window = window;
+        return launch_decode_chunk_window(wp, a->dtype, a->head_dim, (hipStream_t)stream);
+    }
+    return launch_decode_chunk_window_sinks(p, a->dtype, a->head_dim, (hipStream_t)stream);
 }
 
 // sfa_decode_chunk over e4m3 caches: the checks of sfa_decode_chunk and the scale check of sfa_decode_kv8; the workspace,
@@ -682,6 +742,28 @@ int sfa_decode_varlen_window(const sfa_decode_args *a, const void *cu_tokens, in
     if (!p.base.cu_tokens) return SFA_OK;       // nothing to do
     p.window = window;
     return launch_decode_varlen_window(p, a->dtype, a->head_dim, (hipStream_t)stream);
+}
+
+// sfa_decode_varlen_window with an attention sink per query head.  sinks == NULL: the call is sfa_decode_varlen_window's
+int sfa_decode_varlen_window_sinks(const sfa_decode_args *a, const float *sinks, const void *cu_tokens, int total_tokens,
+                                   int64_t qkv_token_stride, int window, void *stream) {
+    VarlenWindowSinksKernelParams p;
+    memset(&p, 0, sizeof(p));
+    // (before varlen_call, whose last check is the workspace)
+    if (a && ((uintptr_t)sinks & 3)) return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_varlen_window_sinks: sinks must be 4-byte aligned");
+    if (const int rc = varlen_call(kVarlenWindowSinks, a, cu_tokens, total_tokens, qkv_token_stride, true, window, &p.base))
+        return rc;
+    if (!p.base.cu_tokens) return SFA_OK;       // nothing to do
+    p.window = window;
+    p.sinks = sinks;
+    if (!sinks) {
+        VarlenWindowKernelParams wp;
+        memset(&wp, 0, sizeof(wp));
+        wp.base = p.base;
+        wp.window = window;
+        return launch_decode_varlen_window(wp, a->dtype, a->head_dim, (hipStream_t)stream);
+    }
+    return launch_decode_varlen_window_sinks(p, a->dtype, a->head_dim, (hipStream_t)stream);
 }
 
 // sfa_decode_varlen over e4m3 caches: as sfa_decode_chunk_kv8 is to sfa_decode_chunk

@@ -29,6 +29,11 @@
 //
 // The two properties are independent in the kernels, and Kv8WindowGeo<BASE, P> carries both
 // (sfa_decode_chunk_kv8_window / sfa_decode_varlen_kv8_window).
+//
+// An attention sink (sfa_decode_chunk_window_sinks / sfa_decode_varlen_window_sinks) is a third property of that kind:
+// WindowSinkGeo<BASE, P> is WindowGeo with `static constexpr bool kSink = true` and sinks(gp), one fp32 logit per query
+// head.  Only chunk_attn_kernel's epilogue looks at it: the workgroups of split 0 fold the sink into their rows' state, so
+// a row counts it once; the prologue and combine kernels do not look at the flag.
 #pragma once
 #include "decode_chunk_common.h"
 #include "kv8_convert.h"
@@ -52,6 +57,10 @@ template <class GEO> struct geo_window<GEO, std::void_t<decltype(GEO::kWindow)>>
 // Is GEO's cache e4m3 bytes with a scale per kv head?
 template <class GEO, class = void> struct geo_kv8 : std::false_type {};
 template <class GEO> struct geo_kv8<GEO, std::void_t<decltype(GEO::kKv8)>> : std::bool_constant<GEO::kKv8> {};
+
+// Does GEO carry an attention sink per query head?
+template <class GEO, class = void> struct geo_sink : std::false_type {};
+template <class GEO> struct geo_sink<GEO, std::void_t<decltype(GEO::kSink)>> : std::bool_constant<GEO::kSink> {};
 
 // BASE behind a parameter struct P that holds BASE's Params as `base`: what the wrappers below share
 template <class BASE, class P>
@@ -103,6 +112,16 @@ struct Kv8WindowGeo : ForwardGeo<BASE, P> {
     static __device__ __forceinline__ int window(const P &gp) { return gp.window; }
     static __device__ __forceinline__ const float *k_scale(const P &gp) { return gp.k_scale; }
     static __device__ __forceinline__ const float *v_scale(const P &gp) { return gp.v_scale; }
+};
+
+// BASE with a window and an attention sink: P holds BASE's Params as `base`, `window` and `sinks` ([H] fp32, never
+// nullptr).  One wrapper, for Kv8WindowGeo's reason: a sink wrapper around WindowGeo would hide its flag and accessor
+template <class BASE, class P>
+struct WindowSinkGeo : ForwardGeo<BASE, P> {
+    static constexpr bool kWindow = true;
+    static constexpr bool kSink = true;
+    static __device__ __forceinline__ int window(const P &gp) { return gp.window; }
+    static __device__ __forceinline__ const float *sinks(const P &gp) { return gp.sinks; }
 };
 
 // The window's lower mask of a half-tile of fresh scores (mask_half's register layout): keys below lo get -inf
@@ -545,6 +564,25 @@ chunk_attn_kernel(const typename GEO::Params gp) {
 
     // ---- epilogue ----
     float ltot = half_sum(acc.lsum[0]);
+    // SINK: one more stream element of the row's query head -- max sinks[h] log2(e), sum 1, accumulator 0 -- folded in by
+    // the workgroups of split 0 alone, tiles or none (msc = -inf, ltot = 0 then), so that a row counts it once
+    if constexpr (geo_sink<GEO>::value) {
+        if (split == 0) {
+            // (laundered: contracted into `sk - ms` below as one fma, the product's rounding error would stand where 0
+            // belongs when the sink is the max)
+            float sk = GEO::sinks(gp)[hk * G + min(qrow, R - 1) % G] * 1.4426950408889634f;
+            asm volatile("" : "+v"(sk));
+            const float mn = fmaxf(acc.msc[0], sk);
+            const float ms = (mn == ninf()) ? 0.f : mn;
+            const float a1 = fast_exp2(acc.msc[0] - ms);
+#pragma unroll
+            for (int d = 0; d < NDB; ++d)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc.o[0][d][r] *= a1;
+            ltot = __builtin_fmaf(ltot, a1, fast_exp2(sk - ms));
+            acc.msc[0] = mn;
+        }
+    }
     if (PAGED && bad_page) {
         ltot = __builtin_nanf("");
         if (tid == 0) atomicOr(p.status, 2);

@@ -12,14 +12,19 @@
 //   (Pages::set(t, lo, w1)): row = min(max(row, lo), w1 - 1), the mirror of the clamp past the wave's end.
 // Without WINDOW `window` is not looked at and no lower bound is computed anywhere: lo is the literal 0 of an untaken
 // branch, not a value the compiler would have to prove non-negative things about.
+//
+// SINK (decode_window_sinks_kernel.hip): sinks[h] is one more logit of query head h's softmax, with a zero value row.  It
+// takes no part in the tiles: Tiles::merge_store folds it in once, after the merge of the waves, in split 0.  Without
+// SINK `sinks` is not looked at.
 #pragma once
 #include "decode_mfma_common.h"
 
 namespace sfa {
 namespace decode {
 
-template <class Tr, int D, bool NT, bool KLDS, bool PAGED, bool WINDOW>
-__device__ __forceinline__ void mfma16_decode(const DecodeKernelParams &p, const int G, const int window) {
+template <class Tr, int D, bool NT, bool KLDS, bool PAGED, bool WINDOW, bool SINK = false>
+__device__ __forceinline__ void mfma16_decode(const DecodeKernelParams &p, const int G, const int window,
+                                              const float *sinks = nullptr) {
     using Lds = MfmaLds<D>;
     constexpr int LPR = D / 8;                  // lanes (16-byte chunks) per cache row
     constexpr int RPL = 64 / LPR;               // rows one load instruction of a wave covers
@@ -140,7 +145,7 @@ __device__ __forceinline__ void mfma16_decode(const DecodeKernelParams &p, const
         }
     }
 
-    st.merge_store(p, smem, b, hk, split, G, PAGED && pg.bad, 1.0f);
+    st.template merge_store<SINK>(p, smem, b, hk, split, G, PAGED && pg.bad, 1.0f, sinks);
 }
 
 }  // namespace decode

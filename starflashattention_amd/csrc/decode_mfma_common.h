@@ -301,8 +301,13 @@ template <class Tr, int D> struct Tiles {
 
     // Merge the workgroup's waves through LDS (after every wave is done with its tiles) and write the G output rows
     // (num_splits == 1) or partials of this kv head, times out_scale.  bad_page: a page outside the pool was read.
+    // SINK: sinks[h] (natural-log units, not scaled) is one more stream element of query head h -- max sinks[h] log2(e),
+    // sum 1, accumulator 0 -- folded in after the waves' merge by split 0 alone, so a row counts it once whatever the
+    // split count and whether or not split 0 had a tile; the output row and the partials both carry it, and the split
+    // combine is the one of the kernels without a sink.
+    template <bool SINK = false>
     __device__ __forceinline__ void merge_store(const DecodeKernelParams &p, char *smem, int b, int hk, int split, int G,
-                                                bool bad_page, float out_scale) {
+                                                bool bad_page, float out_scale, const float *sinks = nullptr) {
         constexpr int W = kDecodeWaves, LPR = D / 8;
         const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, c = lane & 15, g = lane >> 4;
         const int S = p.num_splits;
@@ -329,6 +334,16 @@ template <class Tr, int D> struct Tiles {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) a2[j] = rw[sb * 8 + j];
                 tot.merge(rw[D], rw[D + 1], a2);
+            }
+            if constexpr (SINK) {
+                if (split == 0) {
+                    const float zero[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                    // launder the product: contracted into the merge's `m2 - max` as one fma it leaves the product's
+                    // rounding error where 0 belongs when the sink IS the max -- 2^(+-1e22) for a sink of -1e30
+                    float sk = sinks[hk * G + q] * 1.4426950408889634f;
+                    asm volatile("" : "+v"(sk));
+                    tot.merge(sk, 1.0f, zero);
+                }
             }
             const long long bh = (long long)b * p.H + hk * G + q;
             if (S == 1) {

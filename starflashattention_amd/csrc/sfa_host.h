@@ -124,6 +124,24 @@ struct WindowKernelParams {
     int window;             // >= 1: the token at pos attends to the rows max(0, pos + 1 - window) .. pos
 };
 
+// sfa_decode_window_sinks / sfa_decode_chunk_window_sinks / sfa_decode_varlen_window_sinks (decode_window_sinks_kernel.hip,
+// decode_chunk_window_sinks_kernel.hip, decode_varlen_window_sinks_kernel.hip): the three windowed calls over 16-bit caches
+// with an attention sink.  The sink pointer rides behind the unchanged parameters, as the window does.
+struct WindowSinksKernelParams {
+    WindowKernelParams base;
+    const float *sinks;     // [H] fp32, one logit per query head (natural-log units, not scaled); never nullptr here
+};
+struct ChunkWindowSinksKernelParams {
+    ChunkKernelParams base;
+    int window;
+    const float *sinks;
+};
+struct VarlenWindowSinksKernelParams {
+    VarlenKernelParams base;
+    int window;
+    const float *sinks;
+};
+
 // sfa_decode_kv8_window (decode_kv8_window_kernel.hip, the body of decode_kv8_body.h with its window): sfa_decode_kv8
 // over the last `window` positions.  The window rides behind the unchanged parameters, so decode_kv8_kernel keeps its
 // argument layout.
@@ -170,6 +188,11 @@ int launch_kv8_quantize(void *dst, const void *src, const float *scale, long lon
 // decode_window_kernel.hip: the sliding-window attention kernel (every group size; one body with launch_decode_gqa_mfma's
 // kernel, decode_mfma16.h) plus the split combine
 int launch_decode_window(const WindowKernelParams &p, int dtype, int head_dim, hipStream_t stream);
+// decode_window_sinks_kernel.hip, decode_chunk_window_sinks_kernel.hip, decode_varlen_window_sinks_kernel.hip: the
+// windowed kernels with the sink flag of their bodies set
+int launch_decode_window_sinks(const WindowSinksKernelParams &p, int dtype, int head_dim, hipStream_t stream);
+int launch_decode_chunk_window_sinks(const ChunkWindowSinksKernelParams &p, int dtype, int head_dim, hipStream_t stream);
+int launch_decode_varlen_window_sinks(const VarlenWindowSinksKernelParams &p, int dtype, int head_dim, hipStream_t stream);
 // decode_kv8_window_kernel.hip: the sliding-window attention kernel over e4m3 caches (one body with launch_decode_kv8's
 // kernel, decode_kv8_body.h) plus the split combine
 int launch_decode_kv8_window(const Kv8WindowKernelParams &p, int dtype, int head_dim, hipStream_t stream);
