@@ -27,6 +27,8 @@
  *   sfa_decode_kv8_window       <- (no reference function: sfa_decode_kv8 over the last `window` positions)
  *   sfa_decode_chunk_kv8        <- (no reference function: sfa_decode_chunk / sfa_decode_varlen over an fp8 KV cache)
  *   sfa_decode_chunk_kv8_window <- (no reference function: those two calls with the sliding window)
+ *   sfa_decode_window_sinks     <- (no reference function: the three windowed calls with an attention sink per head)
+ *   sfa_decode_kv8_window_sinks <- (no reference function: the three windowed fp8 calls with that sink)
  * The Python-facing mha_fwd_cuda (src/flash_api.cpp:42-68) and the C++ template
  * surface (src/flash_attn.h) in this repo are thin layers over these symbols.
  */
@@ -60,7 +62,10 @@ extern "C" {
  *      fp8 KV cache) added under the same version, in the same way; no sizing functions of their own either
  *      sfa_decode_window_sinks, sfa_decode_chunk_window_sinks and sfa_decode_varlen_window_sinks (attention sinks in the
  *      three windowed calls over 16-bit caches) added under the same version, in the same way; no sizing functions of
- *      their own either */
+ *      their own either
+ *      sfa_decode_kv8_window_sinks, sfa_decode_chunk_kv8_window_sinks and sfa_decode_varlen_kv8_window_sinks (attention
+ *      sinks in the three windowed calls over an fp8 KV cache) added under the same version, in the same way; no sizing
+ *      functions of their own either */
 #define SFA_ABI_VERSION 4
 
 typedef enum sfa_status {
@@ -390,8 +395,8 @@ size_t sfa_decode_varlen_window_workspace_bytes(int batch_size, int num_heads, i
  * call each one extends, and sfa_decode_window_workspace_bytes / sfa_decode_chunk_window_workspace_bytes /
  * sfa_decode_varlen_window_workspace_bytes size it; with num_splits <= 0 a workspace that holds fewer splits than the
  * library would pick gets the largest count it holds.
- * Not served: sinks over an fp8 cache (the _kv8 calls do not serve sinks yet), head_dim 256 in the multi-token calls,
- * ring-buffer caches, soft-capping.
+ * Not served: head_dim 256 in the multi-token calls, ring-buffer caches, soft-capping.  (Sinks over an fp8 cache:
+ * sfa_decode_kv8_window_sinks / sfa_decode_chunk_kv8_window_sinks / sfa_decode_varlen_kv8_window_sinks, below.)
  */
 int sfa_decode_window_sinks(const sfa_decode_args *args, const float *sinks, int window, void *stream);
 int sfa_decode_chunk_window_sinks(const sfa_decode_args *args, const float *sinks, int num_tokens,
@@ -426,9 +431,9 @@ int sfa_decode_varlen_window_sinks(const sfa_decode_args *args, const float *sin
  * sfa_decode_window_workspace_bytes sizes it.  A workspace sized by sfa_decode_workspace_bytes_gqa is never too small;
  * with num_splits <= 0 one that holds fewer splits than the library would pick gets the largest count it holds.  The
  * same workspace and status word serve every decode entry point on a stream.
- * Not served: head_dim 256, per-token or per-block scales, ring-buffer caches, attention sinks (the _sinks calls serve
- * 16-bit caches only; the fp8 calls do not serve sinks yet), soft-capping.  (More
- * than one token per sequence: sfa_decode_chunk_kv8_window / sfa_decode_varlen_kv8_window, below.)
+ * Not served: head_dim 256, per-token or per-block scales, ring-buffer caches, soft-capping.  (More than one token per
+ * sequence: sfa_decode_chunk_kv8_window / sfa_decode_varlen_kv8_window, below.  Attention sinks:
+ * sfa_decode_kv8_window_sinks, below.)
  */
 int sfa_decode_kv8_window(const sfa_decode_args *args, const float *k_scale, const float *v_scale, int window,
                           void *stream);
@@ -500,14 +505,56 @@ int sfa_decode_varlen_kv8(const sfa_decode_args *args, const float *k_scale, con
  * sfa_decode_varlen_window_workspace_bytes size it; a workspace sized by sfa_decode_chunk_workspace_bytes /
  * sfa_decode_varlen_workspace_bytes is never too small.  The same workspace and status word serve every decode entry
  * point on a stream.
- * Not served: head_dim 256, per-token or per-block scales, ring-buffer caches, attention sinks (the _sinks calls serve
- * 16-bit caches only; the fp8 calls do not serve sinks yet), soft-capping, fp8 matrix instructions on a quantised Q.
+ * Not served: head_dim 256, per-token or per-block scales, ring-buffer caches, soft-capping, fp8 matrix instructions on a
+ * quantised Q.  (Attention sinks: sfa_decode_chunk_kv8_window_sinks / sfa_decode_varlen_kv8_window_sinks, below.)
  */
 int sfa_decode_chunk_kv8_window(const sfa_decode_args *args, const float *k_scale, const float *v_scale, int num_tokens,
                                 int64_t qkv_token_stride, int window, void *stream);
 int sfa_decode_varlen_kv8_window(const sfa_decode_args *args, const float *k_scale, const float *v_scale,
                                  const void *cu_tokens, int total_tokens, int64_t qkv_token_stride, int window,
                                  void *stream);
+
+/* ---- sliding-window decode with attention sinks over an fp8 KV cache ---------------- */
+/*
+ * sfa_decode_kv8_window / sfa_decode_chunk_kv8_window / sfa_decode_varlen_kv8_window for a layer whose softmax carries a
+ * learned per-head sink logit: each call is its _kv8_window twin plus the sink rule of sfa_decode_window_sinks.
+ * Everything of the _kv8_window call each one extends holds unchanged: the caches are e4m3 bytes in the three layouts;
+ * fp16 / bf16; head_dim 64 / 128 (256 returns SFA_ERR_UNSUPPORTED_HEAD_DIM); num_heads / num_heads_kv in {1, 2, 4, 8, 16};
+ * bias, RoPE, the rotary tables, partial rotary; k_scale / v_scale device fp32 [num_heads_kv], NULL = 1.0, 4-byte aligned
+ * (checked, in the twin's place among its checks); the quantised append -- row pos (+ t) receives k8 = q8(k16 /
+ * k_scale[hk]), v8 = q8(v16 / v_scale[hk]), no other byte of a cache changes, and the new tokens attend through their
+ * stored bytes; rows below lo / lo_0 and the block_table entries of pages wholly below the window are never read; the
+ * cu_tokens rules, the rejection rules and the status bits; the call allocates nothing, never synchronises and may be
+ * captured in a graph.  A layer with full attention passes window >= memory_max_len (INT_MAX works); window < 1 returns
+ * SFA_ERR_BAD_SHAPE.
+ *   sinks           device fp32 [num_heads], one logit per QUERY head, 4-byte aligned (checked first: otherwise
+ *                   SFA_ERR_BAD_SHAPE).  Every value is finite or -inf (the caller's contract, not checked).  Read on
+ *                   the device only: a replayed graph sees new contents.
+ *                   NULL: the call validates under its own name and then launches exactly what the _kv8_window call
+ *                   launches; output and caches are bit-identical to it.
+ * Semantics, for query head h of kv head hk over its key range [lo, pos] (chunk / varlen: [lo_t, pos + t]) of the cache
+ * after the append, s_j = q16 . (k_scale[hk] * K8_j) * head_dim_inv:
+ *   o[h] = v_scale[hk] * sum_j exp(s_j) V8_j / (exp(sinks[h]) + sum_j exp(s_j))
+ * -- one more key with logit sinks[h] and a zero value row.  The sink is multiplied NEITHER by head_dim_inv NOR by
+ * k_scale: it is a logit, not a key.  The caches receive exactly what the _kv8_window call stores.
+ * Numerics: the sink joins the online softmax once per query row, whatever the split count.  A sink far above the scores
+ * gives a small finite output, with no overflow; a sink whose weight underflows in fp32 (-inf and -1e30 are two) gives
+ * the _kv8_window call's output bit for bit at the same explicit num_splits.
+ * Workspace: there are no sizing functions of their own.  Layout, split rule and status word are those of the
+ * _kv8_window call each one extends, and sfa_decode_window_workspace_bytes / sfa_decode_chunk_window_workspace_bytes /
+ * sfa_decode_varlen_window_workspace_bytes size it; with num_splits <= 0 a workspace that holds fewer splits than the
+ * library would pick gets the largest count it holds.
+ * Not served: sinks on the calls without a window argument (window >= memory_max_len serves them), head_dim 256,
+ * per-token or per-block scales, ring-buffer caches, soft-capping, fp8 matrix instructions on a quantised Q.
+ */
+int sfa_decode_kv8_window_sinks(const sfa_decode_args *args, const float *k_scale, const float *v_scale,
+                                const float *sinks, int window, void *stream);
+int sfa_decode_chunk_kv8_window_sinks(const sfa_decode_args *args, const float *k_scale, const float *v_scale,
+                                      const float *sinks, int num_tokens, int64_t qkv_token_stride, int window,
+                                      void *stream);
+int sfa_decode_varlen_kv8_window_sinks(const sfa_decode_args *args, const float *k_scale, const float *v_scale,
+                                       const float *sinks, const void *cu_tokens, int total_tokens,
+                                       int64_t qkv_token_stride, int window, void *stream);
 
 /* ---- prefill: O = softmax(mask(Q K^T * scale)) V ------------------------------- */
 /*

@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = [
     "sfa_decode_chunk_kv8", "sfa_decode_varlen_kv8",
     "sfa_decode_chunk_kv8_window", "sfa_decode_varlen_kv8_window",
     "sfa_decode_window_sinks", "sfa_decode_chunk_window_sinks", "sfa_decode_varlen_window_sinks",
+    "sfa_decode_kv8_window_sinks", "sfa_decode_chunk_kv8_window_sinks", "sfa_decode_varlen_kv8_window_sinks",
 ]
 
 
@@ -158,6 +159,17 @@ def load():
     lib.sfa_decode_varlen_window_sinks.restype = ctypes.c_int
     lib.sfa_decode_varlen_window_sinks.argtypes = [ctypes.POINTER(DecodeArgs), ctypes.c_void_p, ctypes.c_void_p,
                                                    ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]
+    lib.sfa_decode_kv8_window_sinks.restype = ctypes.c_int
+    lib.sfa_decode_kv8_window_sinks.argtypes = [ctypes.POINTER(DecodeArgs), ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+    lib.sfa_decode_chunk_kv8_window_sinks.restype = ctypes.c_int
+    lib.sfa_decode_chunk_kv8_window_sinks.argtypes = [ctypes.POINTER(DecodeArgs), ctypes.c_void_p, ctypes.c_void_p,
+                                                      ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+                                                      ctypes.c_void_p]
+    lib.sfa_decode_varlen_kv8_window_sinks.restype = ctypes.c_int
+    lib.sfa_decode_varlen_kv8_window_sinks.argtypes = [ctypes.POINTER(DecodeArgs), ctypes.c_void_p, ctypes.c_void_p,
+                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
+                                                       ctypes.c_int, ctypes.c_void_p]
     lib.sfa_prefill_fwd.restype = ctypes.c_int
     lib.sfa_prefill_fwd.argtypes = [ctypes.POINTER(PrefillArgs), ctypes.c_void_p]
     lib.sfa_compute_rotary_table.restype = ctypes.c_int

@@ -32,7 +32,8 @@ KERNEL_SOURCES = ["prefill_w4_kernel.hip", "prefill_w4_kernel_p1.hip", "prefill_
                   "decode_chunk_kv8_kernel.hip", "decode_varlen_kv8_kernel.hip",
                   "decode_chunk_kv8_window_kernel.hip", "decode_varlen_kv8_window_kernel.hip",
                   "decode_chunk_window_sinks_kernel.hip", "decode_varlen_window_sinks_kernel.hip",
-                  "decode_window_sinks_kernel.hip", "decode_kernel.hip", "decode_gqa_kernel.hip", "decode_gqa_mfma_kernel.hip", "decode_kv8_kernel.hip", "decode_kv8_window_kernel.hip", "decode_window_kernel.hip",
+                  "decode_chunk_kv8_window_sinks_kernel.hip", "decode_varlen_kv8_window_sinks_kernel.hip",
+                  "decode_window_sinks_kernel.hip", "decode_kv8_window_sinks_kernel.hip", "decode_kernel.hip", "decode_gqa_kernel.hip", "decode_gqa_mfma_kernel.hip", "decode_kv8_kernel.hip", "decode_kv8_window_kernel.hip", "decode_window_kernel.hip",
                   "prefill_d256_kernel.hip",
                   "prefill_kernel.hip", "prefill_kernel_bm128.hip", "prefill_dispatch.hip", "decode_dispatch.hip",
                   "aux_kernels.hip", "c_api.hip", "cxx_surface.hip"]

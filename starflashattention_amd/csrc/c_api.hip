@@ -153,6 +153,9 @@ constexpr EntryPoint kChunkKv8 = {"sfa_decode_chunk_kv8", "num_tokens", false, t
 constexpr EntryPoint kVarlenKv8 = {"sfa_decode_varlen_kv8", "total_tokens", false, true, true};
 constexpr EntryPoint kChunkKv8Window = {"sfa_decode_chunk_kv8_window", "num_tokens", false, true, false};
 constexpr EntryPoint kVarlenKv8Window = {"sfa_decode_varlen_kv8_window", "total_tokens", false, true, true};
+constexpr EntryPoint kKv8WindowSinks = {"sfa_decode_kv8_window_sinks", "num_tokens", true, false, false};
+constexpr EntryPoint kChunkKv8WindowSinks = {"sfa_decode_chunk_kv8_window_sinks", "num_tokens", false, true, false};
+constexpr EntryPoint kVarlenKv8WindowSinks = {"sfa_decode_varlen_kv8_window_sinks", "total_tokens", false, true, true};
 
 // What the entry points check alike, before any HIP call, and what they derive on the way.  sfa_decode is the case of
 // one token per sequence (count = 1) with no token stride.
@@ -466,18 +469,20 @@ int sfa_decode_window_sinks(const sfa_decode_args *a, const float *sinks, int wi
 }
 
 // sfa_decode_kv8 with a sliding window: the checks of sfa_decode_kv8 and sfa_decode_window; the workspace, its split
-// rule and the status word are sfa_decode_window's
-int sfa_decode_kv8_window(const sfa_decode_args *a, const float *k_scale, const float *v_scale, int window,
-                          void *stream) {
+// rule and the status word are sfa_decode_window's.  This is the call and its twin with attention sinks up to the launch:
+// the checks, the split count, the workspace and the kernel parameters.  *run = false: nothing to do
+static int kv8_window_call(const EntryPoint &e, const sfa_decode_args *a, const float *k_scale, const float *v_scale,
+                           int window, Kv8WindowKernelParams *out, bool *run) {
     DecodeCall dc;
-    if (const int rc = validate_decode_call(kKv8Window, a, 1, 0, &dc)) return rc;
+    *run = false;
+    if (const int rc = validate_decode_call(e, a, 1, 0, &dc)) return rc;
     if (a->head_dim == 256)
         return fail(SFA_ERR_UNSUPPORTED_HEAD_DIM,
-                    "sfa_decode_kv8_window: head_dim 256 is not supported over an fp8 cache yet (64 or 128; "
-                    "sfa_decode_window serves 256 on a 16-bit cache)");
+                    "%s: head_dim 256 is not supported over an fp8 cache yet (64 or 128; "
+                    "sfa_decode_window serves 256 on a 16-bit cache)", e.fn);
     if (((uintptr_t)k_scale | (uintptr_t)v_scale) & 3)
-        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_kv8_window: k_scale / v_scale must be 4-byte aligned");
-    if (window < 1) return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_kv8_window: window=%d must be >= 1", window);
+        return fail(SFA_ERR_BAD_SHAPE, "%s: k_scale / v_scale must be 4-byte aligned", e.fn);
+    if (window < 1) return fail(SFA_ERR_BAD_SHAPE, "%s: window=%d must be >= 1", e.fn, window);
     if (a->batch_size == 0) return SFA_OK;
 
     const size_t bh = (size_t)a->batch_size * a->num_heads;
@@ -487,10 +492,9 @@ int sfa_decode_kv8_window(const sfa_decode_args *a, const float *k_scale, const 
     if (a->num_splits <= 0 && a->workspace)
         while (S > 1 && a->workspace_bytes < decode_workspace(0, 0, bh, S, a->head_dim).total) --S;
     const DecodeWorkspace w = decode_workspace(0, 0, bh, S, a->head_dim);
-    if (const int rc = check_workspace(kKv8Window, a, w.total)) return rc;
+    if (const int rc = check_workspace(e, a, w.total)) return rc;
 
-    Kv8WindowKernelParams p;
-    memset(&p, 0, sizeof(p));
+    Kv8WindowKernelParams &p = *out;
     p.base.d = decode_params(a, dc.hkv, dc.page_shift, S, dc.stride);
     char *ws = (char *)a->workspace;
     p.base.d.part_o = (float *)(ws + w.part_o);
@@ -498,7 +502,34 @@ int sfa_decode_kv8_window(const sfa_decode_args *a, const float *k_scale, const 
     p.base.k_scale = k_scale;
     p.base.v_scale = v_scale;
     p.window = window;
+    *run = true;
+    return SFA_OK;
+}
+
+int sfa_decode_kv8_window(const sfa_decode_args *a, const float *k_scale, const float *v_scale, int window,
+                          void *stream) {
+    Kv8WindowKernelParams p;
+    memset(&p, 0, sizeof(p));
+    bool run;
+    if (const int rc = kv8_window_call(kKv8Window, a, k_scale, v_scale, window, &p, &run)) return rc;
+    if (!run) return SFA_OK;
     return launch_decode_kv8_window(p, a->dtype, a->head_dim, (hipStream_t)stream);
+}
+
+// sfa_decode_kv8_window with an attention sink per query head.  sinks == NULL: the call is sfa_decode_kv8_window's,
+// launch and all
+int sfa_decode_kv8_window_sinks(const sfa_decode_args *a, const float *k_scale, const float *v_scale, const float *sinks,
+                                int window, void *stream) {
+    Kv8WindowSinksKernelParams p;
+    memset(&p, 0, sizeof(p));
+    bool run;
+    if (a && ((uintptr_t)sinks & 3))
+        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_kv8_window_sinks: sinks must be 4-byte aligned");
+    if (const int rc = kv8_window_call(kKv8WindowSinks, a, k_scale, v_scale, window, &p.base, &run)) return rc;
+    if (!run) return SFA_OK;
+    if (!sinks) return launch_decode_kv8_window(p.base, a->dtype, a->head_dim, (hipStream_t)stream);
+    p.sinks = sinks;
+    return launch_decode_kv8_window_sinks(p, a->dtype, a->head_dim, (hipStream_t)stream);
 }
 
 int sfa_kv8_quantize(void *dst, const void *src, const float *scale, int64_t rows, int num_heads_kv, int head_dim,
@@ -783,14 +814,17 @@ int sfa_decode_varlen_kv8(const sfa_decode_args *a, const float *k_scale, const 
 
 // sfa_decode_chunk_kv8 with a sliding window: the checks of sfa_decode_chunk_kv8 and sfa_decode_chunk_window, in the fp8
 // twin's order (scales before the workspace); the workspace, its split rule and the status word are
-// sfa_decode_chunk_window's
-int sfa_decode_chunk_kv8_window(const sfa_decode_args *a, const float *k_scale, const float *v_scale, int num_tokens,
-                                int64_t qkv_token_stride, int window, void *stream) {
+// sfa_decode_chunk_window's.  This is the call and its twin with attention sinks up to the launch; *run = false: nothing
+// to do
+static int chunk_kv8_window_call(const EntryPoint &e, const sfa_decode_args *a, const float *k_scale, const float *v_scale,
+                                 int num_tokens, int64_t qkv_token_stride, int window, ChunkKv8WindowKernelParams *out,
+                                 bool *run) {
     DecodeCall dc;
-    if (const int rc = validate_decode_call(kChunkKv8Window, a, num_tokens, qkv_token_stride, &dc)) return rc;
+    *run = false;
+    if (const int rc = validate_decode_call(e, a, num_tokens, qkv_token_stride, &dc)) return rc;
     if (((uintptr_t)k_scale | (uintptr_t)v_scale) & 3)
-        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk_kv8_window: k_scale / v_scale must be 4-byte aligned");
-    if (window < 1) return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk_kv8_window: window=%d must be >= 1", window);
+        return fail(SFA_ERR_BAD_SHAPE, "%s: k_scale / v_scale must be 4-byte aligned", e.fn);
+    if (window < 1) return fail(SFA_ERR_BAD_SHAPE, "%s: window=%d must be >= 1", e.fn, window);
     if (a->batch_size == 0 || num_tokens == 0) return SFA_OK;
 
     const int rows = num_tokens * dc.group;
@@ -801,33 +835,104 @@ int sfa_decode_chunk_kv8_window(const sfa_decode_args *a, const float *k_scale, 
     if (a->num_splits <= 0 && a->workspace)
         while (S > 1 && a->workspace_bytes < chunk_workspace(a->batch_size, dc.hkv, rows, S, a->head_dim).total) --S;
     const DecodeWorkspace w = chunk_workspace(a->batch_size, dc.hkv, rows, S, a->head_dim);
-    if (const int rc = check_workspace(kChunkKv8Window, a, w.total)) return rc;
+    if (const int rc = check_workspace(e, a, w.total)) return rc;
 
-    ChunkKv8WindowKernelParams p;
-    memset(&p, 0, sizeof(p));
+    ChunkKv8WindowKernelParams &p = *out;
     p.base = chunk_params(a, dc, num_tokens, S, w);
     p.window = window;
     p.k_scale = k_scale;
     p.v_scale = v_scale;
+    *run = true;
+    return SFA_OK;
+}
+
+int sfa_decode_chunk_kv8_window(const sfa_decode_args *a, const float *k_scale, const float *v_scale, int num_tokens,
+                                int64_t qkv_token_stride, int window, void *stream) {
+    ChunkKv8WindowKernelParams p;
+    memset(&p, 0, sizeof(p));
+    bool run;
+    if (const int rc = chunk_kv8_window_call(kChunkKv8Window, a, k_scale, v_scale, num_tokens, qkv_token_stride, window,
+                                             &p, &run))
+        return rc;
+    if (!run) return SFA_OK;
     return launch_decode_chunk_kv8_window(p, a->dtype, a->head_dim, (hipStream_t)stream);
 }
 
-// sfa_decode_varlen_kv8 with a sliding window: as sfa_decode_chunk_kv8_window is to sfa_decode_chunk_kv8
+// sfa_decode_chunk_kv8_window with an attention sink per query head.  sinks == NULL: the call is
+// sfa_decode_chunk_kv8_window's, launch and all
+int sfa_decode_chunk_kv8_window_sinks(const sfa_decode_args *a, const float *k_scale, const float *v_scale,
+                                      const float *sinks, int num_tokens, int64_t qkv_token_stride, int window,
+                                      void *stream) {
+    ChunkKv8WindowKernelParams wp;
+    memset(&wp, 0, sizeof(wp));
+    bool run;
+    if (a && ((uintptr_t)sinks & 3))
+        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk_kv8_window_sinks: sinks must be 4-byte aligned");
+    if (const int rc = chunk_kv8_window_call(kChunkKv8WindowSinks, a, k_scale, v_scale, num_tokens, qkv_token_stride,
+                                             window, &wp, &run))
+        return rc;
+    if (!run) return SFA_OK;
+    if (!sinks) return launch_decode_chunk_kv8_window(wp, a->dtype, a->head_dim, (hipStream_t)stream);
+    ChunkKv8WindowSinksKernelParams p;
+    memset(&p, 0, sizeof(p));
+    p.base = wp.base;
+    p.window = wp.window;
+    p.k_scale = wp.k_scale;
+    p.v_scale = wp.v_scale;
+    p.sinks = sinks;
+    return launch_decode_chunk_kv8_window_sinks(p, a->dtype, a->head_dim, (hipStream_t)stream);
+}
+
+// sfa_decode_varlen_kv8 with a sliding window: as sfa_decode_chunk_kv8_window is to sfa_decode_chunk_kv8.  This is the
+// call and its twin with attention sinks up to the launch; out->base.cu_tokens stays NULL: nothing to do
+static int varlen_kv8_window_call(const EntryPoint &e, const sfa_decode_args *a, const float *k_scale, const float *v_scale,
+                                  const void *cu_tokens, int total_tokens, int64_t qkv_token_stride, int window,
+                                  VarlenKv8WindowKernelParams *out) {
+    VarlenKv8WindowKernelParams &p = *out;
+    // (before varlen_call, whose last check is the workspace: as in sfa_decode_varlen_kv8)
+    if (((uintptr_t)k_scale | (uintptr_t)v_scale) & 3)
+        return fail(SFA_ERR_BAD_SHAPE, "%s: k_scale / v_scale must be 4-byte aligned", e.fn);
+    if (const int rc = varlen_call(e, a, cu_tokens, total_tokens, qkv_token_stride, true, window, &p.base)) return rc;
+    p.window = window;
+    p.k_scale = k_scale;
+    p.v_scale = v_scale;
+    return SFA_OK;
+}
+
 int sfa_decode_varlen_kv8_window(const sfa_decode_args *a, const float *k_scale, const float *v_scale,
                                  const void *cu_tokens, int total_tokens, int64_t qkv_token_stride, int window,
                                  void *stream) {
     VarlenKv8WindowKernelParams p;
     memset(&p, 0, sizeof(p));
-    // (before varlen_call, whose last check is the workspace: as in sfa_decode_varlen_kv8)
-    if (((uintptr_t)k_scale | (uintptr_t)v_scale) & 3)
-        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_varlen_kv8_window: k_scale / v_scale must be 4-byte aligned");
-    if (const int rc = varlen_call(kVarlenKv8Window, a, cu_tokens, total_tokens, qkv_token_stride, true, window, &p.base))
+    if (const int rc = varlen_kv8_window_call(kVarlenKv8Window, a, k_scale, v_scale, cu_tokens, total_tokens,
+                                              qkv_token_stride, window, &p))
         return rc;
     if (!p.base.cu_tokens) return SFA_OK;       // nothing to do
-    p.window = window;
-    p.k_scale = k_scale;
-    p.v_scale = v_scale;
     return launch_decode_varlen_kv8_window(p, a->dtype, a->head_dim, (hipStream_t)stream);
+}
+
+// sfa_decode_varlen_kv8_window with an attention sink per query head.  sinks == NULL: the call is
+// sfa_decode_varlen_kv8_window's, launch and all
+int sfa_decode_varlen_kv8_window_sinks(const sfa_decode_args *a, const float *k_scale, const float *v_scale,
+                                       const float *sinks, const void *cu_tokens, int total_tokens,
+                                       int64_t qkv_token_stride, int window, void *stream) {
+    VarlenKv8WindowKernelParams wp;
+    memset(&wp, 0, sizeof(wp));
+    if (a && ((uintptr_t)sinks & 3))
+        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_varlen_kv8_window_sinks: sinks must be 4-byte aligned");
+    if (const int rc = varlen_kv8_window_call(kVarlenKv8WindowSinks, a, k_scale, v_scale, cu_tokens, total_tokens,
+                                              qkv_token_stride, window, &wp))
+        return rc;
+    if (!wp.base.cu_tokens) return SFA_OK;      // nothing to do
+    if (!sinks) return launch_decode_varlen_kv8_window(wp, a->dtype, a->head_dim, (hipStream_t)stream);
+    VarlenKv8WindowSinksKernelParams p;
+    memset(&p, 0, sizeof(p));
+    p.base = wp.base;
+    p.window = wp.window;
+    p.k_scale = wp.k_scale;
+    p.v_scale = wp.v_scale;
+    p.sinks = sinks;
+    return launch_decode_varlen_kv8_window_sinks(p, a->dtype, a->head_dim, (hipStream_t)stream);
 }
 
 int sfa_prefill_fwd(const sfa_prefill_args *a, void *stream) {

@@ -34,6 +34,8 @@
 // WindowSinkGeo<BASE, P> is WindowGeo with `static constexpr bool kSink = true` and sinks(gp), one fp32 logit per query
 // head.  Only chunk_attn_kernel's epilogue looks at it: the workgroups of split 0 fold the sink into their rows' state, so
 // a row counts it once; the prologue and combine kernels do not look at the flag.
+// Kv8WindowSinkGeo<BASE, P> carries all three (sfa_decode_chunk_kv8_window_sinks / sfa_decode_varlen_kv8_window_sinks,
+// DESIGN.md 5.17).
 #pragma once
 #include "decode_chunk_common.h"
 #include "kv8_convert.h"
@@ -121,6 +123,21 @@ struct WindowSinkGeo : ForwardGeo<BASE, P> {
     static constexpr bool kWindow = true;
     static constexpr bool kSink = true;
     static __device__ __forceinline__ int window(const P &gp) { return gp.window; }
+    static __device__ __forceinline__ const float *sinks(const P &gp) { return gp.sinks; }
+};
+
+// BASE over e4m3 caches with a window and an attention sink: P holds BASE's Params as `base`, `window`, `k_scale`,
+// `v_scale` and `sinks`.  One wrapper again, for the same reason.  The three flags meet in chunk_attn_kernel's epilogue
+// only, in an order that needs no fp8 case: the row's maximum carries k_scale already (c2), so the sink joins it
+// unscaled, and v_scale multiplies the accumulator after the fold, to which the sink added 0
+template <class BASE, class P>
+struct Kv8WindowSinkGeo : ForwardGeo<BASE, P> {
+    static constexpr bool kWindow = true;
+    static constexpr bool kKv8 = true;
+    static constexpr bool kSink = true;
+    static __device__ __forceinline__ int window(const P &gp) { return gp.window; }
+    static __device__ __forceinline__ const float *k_scale(const P &gp) { return gp.k_scale; }
+    static __device__ __forceinline__ const float *v_scale(const P &gp) { return gp.v_scale; }
     static __device__ __forceinline__ const float *sinks(const P &gp) { return gp.sinks; }
 };
 

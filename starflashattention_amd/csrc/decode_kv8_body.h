@@ -13,6 +13,11 @@
 //   0 x NaN in the P V product is NaN -- and 0x7F is a NaN byte -- their rows are re-addressed to row lo, their page index
 //   to lo's page (Pages::set(t, lo, w1)): row = min(max(row, lo), w1 - 1), the mirror of the clamp past the wave's end.
 // Without WINDOW `window` is not looked at and no lower bound is computed anywhere.
+//
+// SINK (decode_kv8_window_sinks_kernel.hip): sinks[h] is one more logit of query head h's softmax, with a zero value row,
+// exactly as in decode_mfma16.h: Tiles::merge_store folds it in once, after the merge of the waves, in split 0.  k_scale
+// is in sl2, so the merged maximum is in the true log2 units the sink lives in and the sink is not scaled; v_scale
+// multiplies the accumulator alone, to which the sink adds 0.  Without SINK `sinks` is not looked at.
 #pragma once
 #include "decode_mfma_common.h"
 #include "kv8_convert.h"
@@ -23,8 +28,8 @@ namespace decode {
 constexpr int kInFlight = 2;                    // tiles a wave keeps in flight in registers (3 measured no better, and
                                                 // 20-30 % slower through a paged cache: DESIGN.md 5.8)
 
-template <class Tr, int D, bool NT, bool PAGED, bool WINDOW>
-__device__ __forceinline__ void kv8_decode(const Kv8KernelParams &kp, const int window) {
+template <class Tr, int D, bool NT, bool PAGED, bool WINDOW, bool SINK = false>
+__device__ __forceinline__ void kv8_decode(const Kv8KernelParams &kp, const int window, const float *sinks = nullptr) {
     using Lds = MfmaLds<D>;
     constexpr int LPR = D / 8;                  // prologue: lanes (8 16-bit elements each) per head row
     constexpr int LP8 = D / 16;                 // lanes (16-byte chunks = 16 elements) per cache row
@@ -146,8 +151,8 @@ __device__ __forceinline__ void kv8_decode(const Kv8KernelParams &kp, const int 
         }
     }
 
-    // v_scale: once, on the fp32 accumulator
-    st.merge_store(p, smem, b, hk, split, G, PAGED && pg.bad, vsc);
+    // v_scale: once, on the fp32 accumulator (SINK: after the fold, whose accumulator is 0)
+    st.template merge_store<SINK>(p, smem, b, hk, split, G, PAGED && pg.bad, vsc, sinks);
 }
 
 }  // namespace decode

@@ -150,6 +150,27 @@ struct Kv8WindowKernelParams {
     int window;             // >= 1: the token at pos attends to the rows max(0, pos + 1 - window) .. pos
 };
 
+// sfa_decode_kv8_window_sinks / sfa_decode_chunk_kv8_window_sinks / sfa_decode_varlen_kv8_window_sinks
+// (decode_kv8_window_sinks_kernel.hip, decode_chunk_kv8_window_sinks_kernel.hip, decode_varlen_kv8_window_sinks_kernel.hip):
+// the three windowed calls over e4m3 caches with an attention sink.  The sink pointer rides behind the unchanged
+// parameters of the call without one.
+struct Kv8WindowSinksKernelParams {
+    Kv8WindowKernelParams base;
+    const float *sinks;     // [H] fp32, one logit per query head (natural-log units, scaled by nothing); never nullptr here
+};
+struct ChunkKv8WindowSinksKernelParams {
+    ChunkKernelParams base;
+    int window;
+    const float *k_scale, *v_scale;
+    const float *sinks;
+};
+struct VarlenKv8WindowSinksKernelParams {
+    VarlenKernelParams base;
+    int window;
+    const float *k_scale, *v_scale;
+    const float *sinks;
+};
+
 struct PrefillKernelParams {
     const uint16_t *q, *k, *v;
     uint16_t *o;
@@ -196,6 +217,13 @@ int launch_decode_varlen_window_sinks(const VarlenWindowSinksKernelParams &p, in
 // decode_kv8_window_kernel.hip: the sliding-window attention kernel over e4m3 caches (one body with launch_decode_kv8's
 // kernel, decode_kv8_body.h) plus the split combine
 int launch_decode_kv8_window(const Kv8WindowKernelParams &p, int dtype, int head_dim, hipStream_t stream);
+// decode_kv8_window_sinks_kernel.hip, decode_chunk_kv8_window_sinks_kernel.hip, decode_varlen_kv8_window_sinks_kernel.hip:
+// the windowed kernels over e4m3 caches with the sink flag of their bodies set
+int launch_decode_kv8_window_sinks(const Kv8WindowSinksKernelParams &p, int dtype, int head_dim, hipStream_t stream);
+int launch_decode_chunk_kv8_window_sinks(const ChunkKv8WindowSinksKernelParams &p, int dtype, int head_dim,
+                                         hipStream_t stream);
+int launch_decode_varlen_kv8_window_sinks(const VarlenKv8WindowSinksKernelParams &p, int dtype, int head_dim,
+                                          hipStream_t stream);
 int launch_prefill(const PrefillKernelParams &p, int dtype, int head_dim, bool causal, hipStream_t stream);
 int launch_prefill_no_keys(const PrefillKernelParams &p, int head_dim, hipStream_t stream);
 int launch_rotary_table(void *cos_t, void *sin_t, int max_seq_len, int rot_dim, int dtype, hipStream_t stream);

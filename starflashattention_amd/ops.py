@@ -25,6 +25,9 @@ libStarFlashAttention.so.  The public operators:
   flash_decode_window_sinks(...) / flash_decode_chunk_window_sinks(...) / flash_decode_varlen_window_sinks(...)  the
                       three windowed calls over 16-bit caches with a learned sink logit per query head in every softmax
                       (new entry points).
+  flash_decode_kv8_window_sinks(...) / flash_decode_chunk_kv8_window_sinks(...) /
+  flash_decode_varlen_kv8_window_sinks(...)  the same sink in the three windowed calls over an fp8 KV cache (new entry
+                      points).
 """
 import ctypes
 import math
@@ -627,6 +630,93 @@ def flash_decode_varlen_window_sinks(qkv, q_bias, k_bias, v_bias, k_cache_table,
         cu = ctypes.c_void_p(cu_tokens.data_ptr())
         _call_decode(dev, a, 0, S, ws,
                      lambda args, stream: lib.sfa_decode_varlen_window_sinks(args, sk, cu, T, 0, W, stream))
+    return o
+
+
+def flash_decode_kv8_window_sinks(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o,
+                                  batch_size, memory_max_len, num_heads, head_dim, rotary_embedding_dim,
+                                  max_input_length, num_layer, idx_layer, window, sinks, *, num_splits=0,
+                                  rotary_cos_table=None, rotary_sin_table=None, softmax_scale=None, kv_layout="blmhd",
+                                  block_table=None, num_heads_kv=None, k_scale=None, v_scale=None):
+    """flash_decode_kv8_window with attention sinks (include/star_flash_attn.h, sfa_decode_kv8_window_sinks): sinks[h], a
+    float32 device tensor [num_heads], is one more logit in query head h's softmax with a zero value row; it is multiplied
+    neither by the softmax scale nor by k_scale.  sinks=None is flash_decode_kv8_window; window >= memory_max_len is full
+    attention with sinks.  Every other argument as in flash_decode_kv8_window.  Returns `o`."""
+    lib = _lib.load()
+    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
+                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
+                                      kv_layout, block_table, num_heads_kv, kv8=True)
+    W = _window_int(window)
+    dev = qkv.device
+    ks, vs = _kv8_scale(k_scale, "k_scale", Hkv, dev), _kv8_scale(v_scale, "v_scale", Hkv, dev)
+    sk = _sinks_ptr(sinks, H, dev)
+    with torch.cuda.device(dev):
+        S = int(num_splits) if num_splits and num_splits > 0 else 0
+        ws = _workspace(dev, lib.sfa_decode_window_workspace_bytes(B, H, Hkv, D, M, W, S))
+        _call_decode(dev, a, (H + 2 * Hkv) * D, S, ws,
+                     lambda args, stream: lib.sfa_decode_kv8_window_sinks(args, ks, vs, sk, W, stream))
+    return o
+
+
+def flash_decode_chunk_kv8_window_sinks(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o,
+                                        batch_size, memory_max_len, num_heads, head_dim, rotary_embedding_dim,
+                                        max_input_length, num_layer, idx_layer, window, sinks, *, num_splits=0,
+                                        rotary_cos_table=None, rotary_sin_table=None, softmax_scale=None,
+                                        kv_layout="blmhd", block_table=None, num_heads_kv=None, k_scale=None,
+                                        v_scale=None):
+    """flash_decode_chunk_kv8_window with attention sinks (include/star_flash_attn.h, sfa_decode_chunk_kv8_window_sinks):
+    the result of n successive flash_decode_kv8_window_sinks calls.  sinks: float32 device tensor [num_heads] or None
+    (= flash_decode_chunk_kv8_window); every other argument as in flash_decode_chunk_kv8_window.  Returns `o`."""
+    lib = _lib.load()
+    _require(isinstance(qkv, torch.Tensor) and qkv.dim() in (4, 5),
+             f"qkv must be [B, n, 3, H, D] or [B, n, H + 2*Hkv, D] (got {tuple(getattr(qkv, 'shape', ()))})")
+    n = int(qkv.shape[1])
+    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
+                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
+                                      kv_layout, block_table, num_heads_kv, tokens=n, kv8=True)
+    W = _window_int(window)
+    dev = qkv.device
+    ks, vs = _kv8_scale(k_scale, "k_scale", Hkv, dev), _kv8_scale(v_scale, "v_scale", Hkv, dev)
+    sk = _sinks_ptr(sinks, H, dev)
+    with torch.cuda.device(dev):
+        S = int(num_splits) if num_splits and num_splits > 0 else 0
+        ws = _workspace(dev, lib.sfa_decode_chunk_window_workspace_bytes(B, H, Hkv, D, M, n, W, S))
+        _call_decode(dev, a, 0, S, ws,
+                     lambda args, stream: lib.sfa_decode_chunk_kv8_window_sinks(args, ks, vs, sk, n, 0, W, stream))
+    return o
+
+
+def flash_decode_varlen_kv8_window_sinks(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o,
+                                         cu_tokens, batch_size, memory_max_len, num_heads, head_dim,
+                                         rotary_embedding_dim, max_input_length, num_layer, idx_layer, window, sinks, *,
+                                         num_splits=0, rotary_cos_table=None, rotary_sin_table=None, softmax_scale=None,
+                                         kv_layout="blmhd", block_table=None, num_heads_kv=None, k_scale=None,
+                                         v_scale=None):
+    """flash_decode_varlen_kv8_window with attention sinks (include/star_flash_attn.h,
+    sfa_decode_varlen_kv8_window_sinks): every packed token gets what flash_decode_chunk_kv8_window_sinks gives it at
+    pos = seq_len[b].  sinks: float32 device tensor [num_heads] or None (= flash_decode_varlen_kv8_window); every other
+    argument as in flash_decode_varlen_kv8_window.  Returns `o`."""
+    lib = _lib.load()
+    _require(isinstance(qkv, torch.Tensor) and qkv.dim() in (3, 4),
+             f"qkv must be [T, 3, H, D] or [T, H + 2*Hkv, D] (got {tuple(getattr(qkv, 'shape', ()))})")
+    T = int(qkv.shape[0])
+    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
+                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
+                                      kv_layout, block_table, num_heads_kv, packed=T, kv8=True)
+    W = _window_int(window)
+    dev = qkv.device
+    ks, vs = _kv8_scale(k_scale, "k_scale", Hkv, dev), _kv8_scale(v_scale, "v_scale", Hkv, dev)
+    sk = _sinks_ptr(sinks, H, dev)
+    _check_gpu_tensor(cu_tokens, "cu_tokens", torch.int32, (B + 1,), dev)
+    with torch.cuda.device(dev):
+        S = int(num_splits) if num_splits and num_splits > 0 else 0
+        ws = _workspace(dev, lib.sfa_decode_varlen_window_workspace_bytes(B, H, Hkv, D, M, T, W, S))
+        cu = ctypes.c_void_p(cu_tokens.data_ptr())
+        _call_decode(dev, a, 0, S, ws,
+                     lambda args, stream: lib.sfa_decode_varlen_kv8_window_sinks(args, ks, vs, sk, cu, T, 0, W, stream))
     return o
 
 
