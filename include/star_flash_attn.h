@@ -29,6 +29,7 @@
  *   sfa_decode_chunk_kv8_window <- (no reference function: those two calls with the sliding window)
  *   sfa_decode_window_sinks     <- (no reference function: the three windowed calls with an attention sink per head)
  *   sfa_decode_kv8_window_sinks <- (no reference function: the three windowed fp8 calls with that sink)
+ *   sfa_prefill_window_fwd      <- (no reference function: sfa_prefill_fwd with a sliding window and attention sinks)
  * The Python-facing mha_fwd_cuda (src/flash_api.cpp:42-68) and the C++ template
  * surface (src/flash_attn.h) in this repo are thin layers over these symbols.
  */
@@ -65,7 +66,9 @@ extern "C" {
  *      their own either
  *      sfa_decode_kv8_window_sinks, sfa_decode_chunk_kv8_window_sinks and sfa_decode_varlen_kv8_window_sinks (attention
  *      sinks in the three windowed calls over an fp8 KV cache) added under the same version, in the same way; no sizing
- *      functions of their own either */
+ *      functions of their own either
+ *      sfa_prefill_window_fwd (the prefill forward with a sliding window and attention sinks) added under the same
+ *      version, beside an unchanged sfa_prefill_args: callers detect it by symbol */
 #define SFA_ABI_VERSION 4
 
 typedef enum sfa_status {
@@ -595,6 +598,46 @@ typedef struct sfa_prefill_args {
 } sfa_prefill_args;
 
 int sfa_prefill_fwd(const sfa_prefill_args *args, void *stream);
+
+/* ---- prefill with a sliding window and attention sinks ------------------------------ */
+/*
+ * sfa_prefill_fwd for a layer whose causal mask is a sliding window and whose softmax may carry a learned per-head sink
+ * logit (gpt-oss: 64 query heads over 8 kv heads, head_dim 64, a 128-row window on every second layer).
+ * Every field of `args` keeps its sfa_prefill_fwd meaning: strides in elements, multiples of 8; 16-byte alignment; GQA by
+ * heads_q % heads_kv == 0; fp16 / bf16; softmax_scale <= 0 means 1/sqrt(head_dim); lse is optional.  Except:
+ *   head_dim        64 or 128; 256 returns SFA_ERR_UNSUPPORTED_HEAD_DIM, as in the multi-token decode calls.
+ *   causal          must be non-zero, otherwise SFA_ERR_BAD_SHAPE: a two-sided window is not served.
+ *   fast_scale      ignored: scores are always the fp32 Q.K^T times the scale in fp32.
+ *   window          >= 1 (window < 1 returns SFA_ERR_BAD_SHAPE).  With lim_i = i + (seqlen_k - seqlen_q) and
+ *                   lo_i = max(0, lim_i + 1 - window), query row i sees the keys [lo_i, lim_i]: the decode calls' window,
+ *                   and flash-attn's window_size = (window - 1, 0).  window = 1 leaves each row its own key;
+ *                   window >= seqlen_k (INT_MAX works) is the causal mask.
+ *   sinks           device fp32 [heads_q], one logit per QUERY head, in natural-log units; it is NOT multiplied by
+ *                   softmax_scale.  4-byte aligned (checked: otherwise SFA_ERR_BAD_SHAPE).  Every value is finite or
+ *                   -inf (the caller's contract, not checked).  Read on the device only: a replayed graph sees new
+ *                   contents.  NULL: no sink.
+ * Semantics, for row i of query head h over j in [lo_i, lim_i], s_j = q_i . k_j * softmax_scale:
+ *   o   = sum_j exp(s_j) V_j / (exp(sinks[h]) + sum_j exp(s_j))
+ *   lse = log(exp(sinks[h]) + sum_j exp(s_j))
+ * -- one more key with logit sinks[h] and a zero value row.  lse is the normaliser of the o that is returned, so
+ * o * exp(lse) is the un-normalised sum.  A row with no visible key (lim_i < 0) gets zeros and lse = -inf, sink or not,
+ * as in sfa_prefill_fwd: the sink joins only a softmax that has a key.  So seqlen_k == 0 writes zeros and -inf exactly as
+ * sfa_prefill_fwd does.
+ * What the window promises: with lo_0 = max(0, seqlen_k - seqlen_q + 1 - window), the bound of the first query row, the K
+ * and V rows below lo_0 are never read; they may hold anything, NaN included.  A workgroup (256 query rows of one head)
+ * reads only the 64-key tiles between its first row's lo and its last row's lim.
+ * Numerics: the sink joins the online softmax once per query row.  A sink far above the scores gives a small finite
+ * output, with no overflow; a sink whose weight underflows in fp32 (-inf and -1e30 are two) gives the output of the same
+ * kernel with no sink, bit for bit.
+ * Forwarding: with sinks == NULL and window >= seqlen_k the call validates under its own name and then launches exactly
+ * what sfa_prefill_fwd(causal = 1, fast_scale = 0) launches; the output is bit-identical to it, and
+ * sfa_debug_get("last_prefill_kernel") reports that kernel.  Every other case -- window >= seqlen_k with sinks included --
+ * runs the windowed kernel (csrc/prefill_window_kernel.hip), after which last_prefill_kernel keeps its previous value.
+ * Like every entry point it is asynchronous on `stream`, allocates nothing, never synchronises and may be captured in a
+ * graph.
+ * Not served: head_dim 256, two-sided windows, soft-capping, a paged or fp8 K/V, split key ranges.
+ */
+int sfa_prefill_window_fwd(const sfa_prefill_args *args, int window, const float *sinks, void *stream);
 
 /* ---- test / A-B hooks: NOT part of the drop-in surface ------------------------------ */
 /* The launch paths read no environment variable; the test-suite and tools/ select kernel

@@ -24,6 +24,7 @@
 
 #include <cmath>
 #include <map>
+#include <climits>
 #include <mutex>
 #include <tuple>
 
@@ -192,10 +193,13 @@ void check_errors() {
     check_status(st, "mha_fwd_cuda");
 }
 
-// Prefill forward: q [B,Hq,Sq,D], k/v [B,Hkv,Sk,D] (head_dim contiguous, any other strides).
-std::vector<at::Tensor> mha_fwd(const at::Tensor &q, const at::Tensor &k, const at::Tensor &v,
-                                c10::optional<at::Tensor> out_, bool causal, double softmax_scale,
-                                bool return_lse, bool fast_scale) {
+// What mha_fwd and mha_fwd_window check and marshal alike: the sfa_prefill_args of q / k / v, the output and the lse
+struct PrefillCall {
+    sfa_prefill_args a;
+    at::Tensor out, lse;
+};
+static PrefillCall prefill_call(const at::Tensor &q, const at::Tensor &k, const at::Tensor &v,
+                                const c10::optional<at::Tensor> &out_, double softmax_scale, bool return_lse) {
     TORCH_CHECK(q.defined() && q.is_cuda(), "star_flash_attn: q must live on a HIP device");
     const int dt = dtype_code(q, "q");
     for (const at::Tensor *t : {&q, &k, &v}) {
@@ -205,16 +209,16 @@ std::vector<at::Tensor> mha_fwd(const at::Tensor &q, const at::Tensor &k, const 
     }
     TORCH_CHECK(k.sizes() == v.sizes() && k.size(0) == q.size(0) && k.size(3) == q.size(3),
                 "star_flash_attn: k/v shapes ", k.sizes(), " / ", v.sizes(), " do not match q ", q.sizes());
-    at::Tensor out = out_.has_value() ? *out_ : at::empty_like(q, q.options(), at::MemoryFormat::Contiguous);
+    PrefillCall c;
+    c.out = out_.has_value() ? *out_ : at::empty_like(q, q.options(), at::MemoryFormat::Contiguous);
+    const at::Tensor &out = c.out;
     TORCH_CHECK(out.sizes() == q.sizes() && out.scalar_type() == q.scalar_type() && out.device() == q.device() &&
                 out.stride(3) == 1, "star_flash_attn: out must match q");
-    at::Tensor lse;
-    if (return_lse) lse = at::empty({q.size(0), q.size(1), q.size(2)}, q.options().dtype(at::kFloat));
+    if (return_lse) c.lse = at::empty({q.size(0), q.size(1), q.size(2)}, q.options().dtype(at::kFloat));
 
-    c10::hip::HIPGuardMasqueradingAsCUDA guard(q.device());
     sfa_prefill_args a = {};
     a.q = q.data_ptr(); a.k = k.data_ptr(); a.v = v.data_ptr(); a.o = out.data_ptr();
-    a.lse = return_lse ? lse.data_ptr<float>() : nullptr;
+    a.lse = return_lse ? c.lse.data_ptr<float>() : nullptr;
     a.batch = (int)q.size(0); a.heads_q = (int)q.size(1); a.heads_kv = (int)k.size(1);
     a.seqlen_q = (int)q.size(2); a.seqlen_k = (int)k.size(2); a.head_dim = (int)q.size(3);
     for (int i = 0; i < 3; ++i) {
@@ -222,12 +226,45 @@ std::vector<at::Tensor> mha_fwd(const at::Tensor &q, const at::Tensor &k, const 
         a.v_stride[i] = v.stride(i); a.o_stride[i] = out.stride(i);
     }
     a.softmax_scale = (float)softmax_scale;
-    a.causal = causal ? 1 : 0;
-    a.fast_scale = fast_scale ? 1 : 0;      // opt-in: prescaled-Q kernels (include/star_flash_attn.h)
     a.dtype = dt;
-    check_status(sfa_prefill_fwd(&a, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(q.device().index()).stream()), "mha_fwd");
-    if (return_lse) return {out, lse};
-    return {out};
+    c.a = a;
+    return c;
+}
+
+// Prefill forward: q [B,Hq,Sq,D], k/v [B,Hkv,Sk,D] (head_dim contiguous, any other strides).
+std::vector<at::Tensor> mha_fwd(const at::Tensor &q, const at::Tensor &k, const at::Tensor &v,
+                                c10::optional<at::Tensor> out_, bool causal, double softmax_scale,
+                                bool return_lse, bool fast_scale) {
+    PrefillCall c = prefill_call(q, k, v, out_, softmax_scale, return_lse);
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(q.device());
+    c.a.causal = causal ? 1 : 0;
+    c.a.fast_scale = fast_scale ? 1 : 0;    // opt-in: prescaled-Q kernels (include/star_flash_attn.h)
+    check_status(sfa_prefill_fwd(&c.a, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(q.device().index()).stream()), "mha_fwd");
+    if (return_lse) return {c.out, c.lse};
+    return {c.out};
+}
+
+// Prefill forward under a sliding window (causal; row i sees the `window` keys that end at its causal limit) with an
+// optional attention sink per query head: sinks fp32 [Hq] on q's device (include/star_flash_attn.h).
+std::vector<at::Tensor> mha_fwd_window(const at::Tensor &q, const at::Tensor &k, const at::Tensor &v, int64_t window,
+                                       c10::optional<at::Tensor> sinks_, double softmax_scale, bool return_lse) {
+    PrefillCall c = prefill_call(q, k, v, c10::nullopt, softmax_scale, return_lse);
+    TORCH_CHECK(window >= 1 && window <= INT_MAX, "star_flash_attn: window must be in [1, INT_MAX], got ", window);
+    const float *sinks = nullptr;
+    if (sinks_.has_value()) {
+        const at::Tensor &s = *sinks_;
+        TORCH_CHECK(s.is_cuda() && s.device() == q.device() && s.scalar_type() == at::kFloat && s.dim() == 1 &&
+                    s.size(0) == q.size(1) && s.is_contiguous(),
+                    "star_flash_attn: sinks must be a contiguous float32 [heads_q] tensor on q's device");
+        sinks = s.data_ptr<float>();
+    }
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(q.device());
+    c.a.causal = 1;
+    check_status(sfa_prefill_window_fwd(&c.a, (int)window, sinks,
+                                        c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(q.device().index()).stream()),
+                 "mha_fwd_window");
+    if (return_lse) return {c.out, c.lse};
+    return {c.out};
 }
 
 std::vector<at::Tensor> compute_rotary_table(int max_seq_len, int rot_dim, at::ScalarType dtype, at::Device device) {
@@ -257,6 +294,10 @@ PYBIND11_MODULE(star_flash_attn, m) {
     m.def("mha_fwd", &mha_fwd, "Attention forward (prefill): returns [out] or [out, lse]",
           py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out") = py::none(), py::arg("causal") = false,
           py::arg("softmax_scale") = 0.0, py::arg("return_lse") = false, py::arg("fast_scale") = false);
+    m.def("mha_fwd_window", &mha_fwd_window,
+          "Attention forward (prefill) under a sliding window with optional attention sinks: returns [out] or [out, lse]",
+          py::arg("q"), py::arg("k"), py::arg("v"), py::arg("window"), py::arg("sinks") = py::none(),
+          py::arg("softmax_scale") = 0.0, py::arg("return_lse") = false);
     m.def("compute_rotary_table", &compute_rotary_table, "cos/sin LUT [max_seq_len, rot_dim/2]",
           py::arg("max_seq_len"), py::arg("rot_dim"), py::arg("dtype"), py::arg("device"));
 }

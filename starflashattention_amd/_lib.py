@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = [
     "sfa_decode_chunk_kv8_window", "sfa_decode_varlen_kv8_window",
     "sfa_decode_window_sinks", "sfa_decode_chunk_window_sinks", "sfa_decode_varlen_window_sinks",
     "sfa_decode_kv8_window_sinks", "sfa_decode_chunk_kv8_window_sinks", "sfa_decode_varlen_kv8_window_sinks",
+    "sfa_prefill_window_fwd",
 ]
 
 
@@ -172,6 +173,8 @@ def load():
                                                        ctypes.c_int, ctypes.c_void_p]
     lib.sfa_prefill_fwd.restype = ctypes.c_int
     lib.sfa_prefill_fwd.argtypes = [ctypes.POINTER(PrefillArgs), ctypes.c_void_p]
+    lib.sfa_prefill_window_fwd.restype = ctypes.c_int
+    lib.sfa_prefill_window_fwd.argtypes = [ctypes.POINTER(PrefillArgs), ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     lib.sfa_compute_rotary_table.restype = ctypes.c_int
     lib.sfa_compute_rotary_table.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                              ctypes.c_int, ctypes.c_int, ctypes.c_void_p]

@@ -935,31 +935,39 @@ int sfa_decode_varlen_kv8_window_sinks(const sfa_decode_args *a, const float *k_
     return launch_decode_varlen_kv8_window_sinks(p, a->dtype, a->head_dim, (hipStream_t)stream);
 }
 
-int sfa_prefill_fwd(const sfa_prefill_args *a, void *stream) {
-    if (!a) return fail(SFA_ERR_NULL_POINTER, "sfa_prefill_fwd: args is NULL");
+}  // extern "C"
+
+namespace {
+
+// What sfa_prefill_fwd and sfa_prefill_window_fwd check and marshal alike, under the name of the call.  d256: head_dim
+// 256 is served.  Returns a status; *launch is false where there is nothing to do (batch or seqlen_q of 0).  p->nq_tiles
+// and p->bh_per_xcd are set for seqlen_k > 0.
+int prefill_call(const char *name, const sfa_prefill_args *a, bool d256, PrefillKernelParams *pp, bool *launch) {
+    *launch = false;
+    if (!a) return fail(SFA_ERR_NULL_POINTER, "%s: args is NULL", name);
     if (!a->q || !a->k || !a->v || !a->o)
-        return fail(SFA_ERR_NULL_POINTER, "sfa_prefill_fwd: q/k/v/o must be non-NULL");
+        return fail(SFA_ERR_NULL_POINTER, "%s: q/k/v/o must be non-NULL", name);
     if (a->batch < 0 || a->heads_q <= 0 || a->heads_kv <= 0 || a->seqlen_q < 0 || a->seqlen_k < 0)
-        return fail(SFA_ERR_BAD_SHAPE, "sfa_prefill_fwd: batch=%d heads_q=%d heads_kv=%d seqlen_q=%d seqlen_k=%d",
+        return fail(SFA_ERR_BAD_SHAPE, "%s: batch=%d heads_q=%d heads_kv=%d seqlen_q=%d seqlen_k=%d", name,
                     a->batch, a->heads_q, a->heads_kv, a->seqlen_q, a->seqlen_k);
     if (a->heads_q % a->heads_kv)
-        return fail(SFA_ERR_BAD_SHAPE, "sfa_prefill_fwd: heads_q=%d not a multiple of heads_kv=%d", a->heads_q, a->heads_kv);
-    if (a->head_dim != 64 && a->head_dim != 128 && a->head_dim != 256)
-        return fail(SFA_ERR_UNSUPPORTED_HEAD_DIM, "sfa_prefill_fwd: head_dim %d not in {64, 128, 256}", a->head_dim);
+        return fail(SFA_ERR_BAD_SHAPE, "%s: heads_q=%d not a multiple of heads_kv=%d", name, a->heads_q, a->heads_kv);
+    if (a->head_dim != 64 && a->head_dim != 128 && !(d256 && a->head_dim == 256))
+        return fail(SFA_ERR_UNSUPPORTED_HEAD_DIM, "%s: head_dim %d not in {64, 128%s}", name, a->head_dim, d256 ? ", 256" : "");
     if (a->dtype != SFA_DTYPE_FP16 && a->dtype != SFA_DTYPE_BF16)
-        return fail(SFA_ERR_BAD_DTYPE, "sfa_prefill_fwd: dtype %d is not fp16(0)/bf16(1)", a->dtype);
+        return fail(SFA_ERR_BAD_DTYPE, "%s: dtype %d is not fp16(0)/bf16(1)", name, a->dtype);
     const int64_t *st[4] = {a->q_stride, a->k_stride, a->v_stride, a->o_stride};
     for (int t = 0; t < 4; ++t)
         for (int i = 0; i < 3; ++i)
             if (st[t][i] < 0 || (st[t][i] % 8) != 0)
-                return fail(SFA_ERR_BAD_SHAPE, "sfa_prefill_fwd: strides must be >= 0 and multiples of 8 elements");
+                return fail(SFA_ERR_BAD_SHAPE, "%s: strides must be >= 0 and multiples of 8 elements", name);
     if (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->o) & 15)
-        return fail(SFA_ERR_BAD_SHAPE, "sfa_prefill_fwd: tensors must be 16-byte aligned");
+        return fail(SFA_ERR_BAD_SHAPE, "%s: tensors must be 16-byte aligned", name);
     if ((long long)a->batch * a->heads_q > (1ll << 24))
-        return fail(SFA_ERR_BAD_SHAPE, "sfa_prefill_fwd: batch*heads_q too large");
+        return fail(SFA_ERR_BAD_SHAPE, "%s: batch*heads_q too large", name);
     if (a->batch == 0 || a->seqlen_q == 0) return SFA_OK;
 
-    PrefillKernelParams p;
+    PrefillKernelParams &p = *pp;
     memset(&p, 0, sizeof(p));
     p.q = (const uint16_t *)a->q;
     p.k = (const uint16_t *)a->k;
@@ -980,13 +988,47 @@ int sfa_prefill_fwd(const sfa_prefill_args *a, void *stream) {
     }
     const float scale = a->softmax_scale > 0.f ? a->softmax_scale : 1.0f / std::sqrt((float)a->head_dim);
     p.scale_log2 = scale * 1.4426950408889634f;
-    if (a->seqlen_k == 0)       // no keys: every row is empty -> zeros, lse = -inf (the header's promise)
-        return launch_prefill_no_keys(p, a->head_dim, (hipStream_t)stream);
+    *launch = true;
+    if (a->seqlen_k == 0) return SFA_OK;
     p.nq_tiles = (a->seqlen_q + 255) / 256;
     p.bh_per_xcd = (a->batch * a->heads_q + 7) / 8;
     if ((long long)8 * p.bh_per_xcd * p.nq_tiles > 0x7fffffffll)
-        return fail(SFA_ERR_BAD_SHAPE, "sfa_prefill_fwd: grid too large");
+        return fail(SFA_ERR_BAD_SHAPE, "%s: grid too large", name);
+    return SFA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sfa_prefill_fwd(const sfa_prefill_args *a, void *stream) {
+    PrefillKernelParams p;
+    bool launch;
+    if (const int rc = prefill_call("sfa_prefill_fwd", a, true, &p, &launch)) return rc;
+    if (!launch) return SFA_OK;
+    if (a->seqlen_k == 0)       // no keys: every row is empty -> zeros, lse = -inf (the header's promise)
+        return launch_prefill_no_keys(p, a->head_dim, (hipStream_t)stream);
     return launch_prefill(p, a->dtype, a->head_dim, a->causal != 0, (hipStream_t)stream);
+}
+
+// sfa_prefill_fwd under a sliding window, with an optional attention sink per query head.  No sink and a window that
+// covers every key: the call is sfa_prefill_fwd's (causal, exact scale), launch and all
+int sfa_prefill_window_fwd(const sfa_prefill_args *a, int window, const float *sinks, void *stream) {
+    static const char *const name = "sfa_prefill_window_fwd";
+    PrefillWindowKernelParams wp;
+    bool launch;
+    if (a && ((uintptr_t)sinks & 3)) return fail(SFA_ERR_BAD_SHAPE, "%s: sinks must be 4-byte aligned", name);
+    if (a && !a->causal) return fail(SFA_ERR_BAD_SHAPE, "%s: causal must be non-zero (a two-sided window is not served)", name);
+    if (a && window < 1) return fail(SFA_ERR_BAD_SHAPE, "%s: window=%d must be >= 1", name, window);
+    if (const int rc = prefill_call(name, a, false, &wp.base, &launch)) return rc;
+    if (!launch) return SFA_OK;
+    wp.base.fast_scale = 0;
+    if (a->seqlen_k == 0)       // no keys: zeros and lse = -inf, sink or not
+        return launch_prefill_no_keys(wp.base, a->head_dim, (hipStream_t)stream);
+    if (!sinks && window >= a->seqlen_k) return launch_prefill(wp.base, a->dtype, a->head_dim, true, (hipStream_t)stream);
+    wp.window = window < a->seqlen_k ? window : a->seqlen_k;    // a longer window is the causal mask
+    wp.sinks = sinks;
+    return launch_prefill_window(wp, a->dtype, a->head_dim, (hipStream_t)stream);
 }
 
 int sfa_compute_rotary_table(void *cos_table, void *sin_table, int max_seq_len, int rot_dim, int dtype,

@@ -184,6 +184,14 @@ struct PrefillKernelParams {
     int fast_scale;         // caller allows the prescaled-Q flavour (only used when lse == nullptr)
 };
 
+// sfa_prefill_window_fwd (prefill_window_kernel.hip): the prefill forward with a sliding window and an optional attention
+// sink.  Window and sink ride behind the unchanged parameters, so the prefill kernels keep their argument layout.
+struct PrefillWindowKernelParams {
+    PrefillKernelParams base;   // every field keeps its meaning; nq_tiles = q-tiles (256 rows) per (batch, head)
+    int window;             // >= 1: row i with causal limit lim sees the keys max(0, lim + 1 - window) .. lim
+    const float *sinks;     // [Hq] fp32, one logit per query head (natural-log units, not scaled), or nullptr
+};
+
 int launch_decode(const DecodeKernelParams &p, int dtype, int head_dim, hipStream_t stream);     // decode_dispatch.hip
 // non-temporal cache loads? (both caches of elem_bytes per element against the Infinity Cache, or the decode_nt knob)
 bool decode_nt(const DecodeKernelParams &p, int head_dim, int elem_bytes);                       // decode_dispatch.hip
@@ -226,6 +234,8 @@ int launch_decode_varlen_kv8_window_sinks(const VarlenKv8WindowSinksKernelParams
                                           hipStream_t stream);
 int launch_prefill(const PrefillKernelParams &p, int dtype, int head_dim, bool causal, hipStream_t stream);
 int launch_prefill_no_keys(const PrefillKernelParams &p, int head_dim, hipStream_t stream);
+// prefill_window_kernel.hip: called by sfa_prefill_window_fwd only (validated dtype, head_dim 64 / 128, Sk > 0)
+int launch_prefill_window(const PrefillWindowKernelParams &p, int dtype, int head_dim, hipStream_t stream);
 int launch_rotary_table(void *cos_t, void *sin_t, int max_seq_len, int rot_dim, int dtype, hipStream_t stream);
 int launch_fill16(void *arr, uint16_t bits, size_t n, hipStream_t stream);
 

@@ -735,12 +735,8 @@ def check_decode_status(device=None):
         _lib.check(st)
 
 
-def flash_attn_fwd(q, k, v, causal=False, softmax_scale=None, out=None, return_lse=False, fast_scale=False):
-    """O = softmax(mask(Q K^T * scale)) V.   q [B,Hq,Sq,D], k/v [B,Hkv,Sk,D] (any batch/head/seq
-    strides, D contiguous), fp16 or bf16, D in {64,128,256}.  causal is bottom-right aligned.
-    fast_scale=True (ignored with return_lse) allows the prescaled-Q kernels: ~5 % faster, the scale is
-    folded into Q in 16 bit, so the score error grows with the logits (include/star_flash_attn.h)."""
-    lib = _lib.load()
+def _prefill_args(q, k, v, out, return_lse, softmax_scale):
+    """The checks and the sfa_prefill_args of flash_attn_fwd and flash_attn_window_fwd: (args, out, lse, device)"""
     _require(isinstance(q, torch.Tensor) and q.dtype in _DTYPES,
              f"q must be float16 or bfloat16 (got {getattr(q, 'dtype', type(q))})")
     dt, dev = q.dtype, q.device
@@ -766,11 +762,38 @@ def flash_attn_fwd(q, k, v, causal=False, softmax_scale=None, out=None, return_l
     for dst, t in ((a.q_stride, q), (a.k_stride, k), (a.v_stride, v), (a.o_stride, out)):
         dst[0], dst[1], dst[2] = t.stride(0), t.stride(1), t.stride(2)
     a.softmax_scale = float(softmax_scale) if softmax_scale else 0.0
-    a.causal = 1 if causal else 0
     a.dtype = _DTYPES[dt]
+    return a, out, lse, dev
+
+
+def flash_attn_fwd(q, k, v, causal=False, softmax_scale=None, out=None, return_lse=False, fast_scale=False):
+    """O = softmax(mask(Q K^T * scale)) V.   q [B,Hq,Sq,D], k/v [B,Hkv,Sk,D] (any batch/head/seq
+    strides, D contiguous), fp16 or bf16, D in {64,128,256}.  causal is bottom-right aligned.
+    fast_scale=True (ignored with return_lse) allows the prescaled-Q kernels: ~5 % faster, the scale is
+    folded into Q in 16 bit, so the score error grows with the logits (include/star_flash_attn.h)."""
+    lib = _lib.load()
+    a, out, lse, dev = _prefill_args(q, k, v, out, return_lse, softmax_scale)
+    a.causal = 1 if causal else 0
     a.fast_scale = 1 if fast_scale else 0
     with torch.cuda.device(dev):
         _lib.check(lib.sfa_prefill_fwd(ctypes.byref(a), _stream_ptr(dev)))
+    return (out, lse) if return_lse else out
+
+
+def flash_attn_window_fwd(q, k, v, window, sinks=None, softmax_scale=None, out=None, return_lse=False):
+    """flash_attn_fwd(causal=True) under a sliding window, with an optional attention sink per query head
+    (sfa_prefill_window_fwd): row i with causal limit lim = i + (Sk - Sq) sees the keys max(0, lim + 1 - window) .. lim --
+    flash-attn's window_size = (window - 1, 0) -- and its softmax counts one more element with logit sinks[h] (natural-log
+    units, not scaled) and a zero value row.  window: an int >= 1 (>= Sk: the causal mask); sinks: None or a float32 [Hq]
+    tensor on q's device; D in {64, 128}.  With return_lse the second result is log(exp(sinks[h]) + sum_j exp(s_j))."""
+    lib = _lib.load()
+    a, out, lse, dev = _prefill_args(q, k, v, out, return_lse, softmax_scale)
+    W = _window_int(window)
+    _require(W >= 1, f"window={window} must be >= 1")
+    a.causal = 1
+    a.fast_scale = 0
+    with torch.cuda.device(dev):
+        _lib.check(lib.sfa_prefill_window_fwd(ctypes.byref(a), W, _sinks_ptr(sinks, q.shape[1], dev), _stream_ptr(dev)))
     return (out, lse) if return_lse else out
 
 
