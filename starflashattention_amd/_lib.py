@@ -106,71 +106,24 @@ def load():
     lib.sfa_decode_reset_status.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     lib.sfa_decode_poll_status.restype = ctypes.c_int
     lib.sfa_decode_poll_status.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    lib.sfa_decode.restype = ctypes.c_int
-    lib.sfa_decode.argtypes = [ctypes.POINTER(DecodeArgs), ctypes.c_void_p]
-    lib.sfa_decode_chunk.restype = ctypes.c_int
-    lib.sfa_decode_chunk.argtypes = [ctypes.POINTER(DecodeArgs), ctypes.c_int, ctypes.c_int64, ctypes.c_void_p]
-    lib.sfa_decode_chunk_workspace_bytes.restype = ctypes.c_size_t
-    lib.sfa_decode_chunk_workspace_bytes.argtypes = [ctypes.c_int] * 7
-    lib.sfa_decode_varlen.restype = ctypes.c_int
-    lib.sfa_decode_varlen.argtypes = [ctypes.POINTER(DecodeArgs), ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
-                                      ctypes.c_void_p]
-    lib.sfa_decode_varlen_workspace_bytes.restype = ctypes.c_size_t
-    lib.sfa_decode_varlen_workspace_bytes.argtypes = [ctypes.c_int] * 7
-    lib.sfa_decode_kv8.restype = ctypes.c_int
-    lib.sfa_decode_kv8.argtypes = [ctypes.POINTER(DecodeArgs), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    # The 18 decode calls, three shapes x six flavours, take (args, [k_scale, v_scale], [sinks], [cu_tokens],
+    # [count, token stride], [window], stream); the sizing function of a shape, with or without a window, takes
+    # (batch_size, num_heads, num_heads_kv, head_dim, memory_max_len, [count], [window], num_splits).
+    P = ctypes.c_void_p
+    for shape, count in (("", []), ("_chunk", [ctypes.c_int, ctypes.c_int64]), ("_varlen", [ctypes.c_int, ctypes.c_int64])):
+        for flavour in ("", "_window", "_window_sinks", "_kv8", "_kv8_window", "_kv8_window_sinks"):
+            fn = getattr(lib, "sfa_decode" + shape + flavour)
+            fn.restype = ctypes.c_int
+            fn.argtypes = ([ctypes.POINTER(DecodeArgs)] + [P, P] * ("_kv8" in flavour) + [P] * ("_sinks" in flavour) +
+                           [P] * (shape == "_varlen") + count + [ctypes.c_int] * ("_window" in flavour) + [P])
+        for window in (0, 1):
+            if shape or window:     # (sfa_decode_workspace_bytes, above, does not take num_heads_kv)
+                fn = getattr(lib, "sfa_decode" + shape + "_window" * window + "_workspace_bytes")
+                fn.restype = ctypes.c_size_t
+                fn.argtypes = [ctypes.c_int] * (6 + bool(shape) + window)
     lib.sfa_kv8_quantize.restype = ctypes.c_int
     lib.sfa_kv8_quantize.argtypes = ([ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_int, ctypes.c_int] +
                                      [ctypes.c_int64] * 4 + [ctypes.c_int, ctypes.c_void_p])
-    lib.sfa_decode_window.restype = ctypes.c_int
-    lib.sfa_decode_window.argtypes = [ctypes.POINTER(DecodeArgs), ctypes.c_int, ctypes.c_void_p]
-    lib.sfa_decode_window_workspace_bytes.restype = ctypes.c_size_t
-    lib.sfa_decode_window_workspace_bytes.argtypes = [ctypes.c_int] * 7
-    lib.sfa_decode_chunk_window.restype = ctypes.c_int
-    lib.sfa_decode_chunk_window.argtypes = [ctypes.POINTER(DecodeArgs), ctypes.c_int, ctypes.c_int64, ctypes.c_int,
-                                            ctypes.c_void_p]
-    lib.sfa_decode_chunk_window_workspace_bytes.restype = ctypes.c_size_t
-    lib.sfa_decode_chunk_window_workspace_bytes.argtypes = [ctypes.c_int] * 8
-    lib.sfa_decode_varlen_window.restype = ctypes.c_int
-    lib.sfa_decode_varlen_window.argtypes = [ctypes.POINTER(DecodeArgs), ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
-                                             ctypes.c_int, ctypes.c_void_p]
-    lib.sfa_decode_varlen_window_workspace_bytes.restype = ctypes.c_size_t
-    lib.sfa_decode_varlen_window_workspace_bytes.argtypes = [ctypes.c_int] * 8
-    lib.sfa_decode_kv8_window.restype = ctypes.c_int
-    lib.sfa_decode_kv8_window.argtypes = [ctypes.POINTER(DecodeArgs), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                          ctypes.c_void_p]
-    lib.sfa_decode_chunk_kv8.restype = ctypes.c_int
-    lib.sfa_decode_chunk_kv8.argtypes = [ctypes.POINTER(DecodeArgs), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                         ctypes.c_int64, ctypes.c_void_p]
-    lib.sfa_decode_varlen_kv8.restype = ctypes.c_int
-    lib.sfa_decode_varlen_kv8.argtypes = [ctypes.POINTER(DecodeArgs), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                          ctypes.c_int, ctypes.c_int64, ctypes.c_void_p]
-    lib.sfa_decode_chunk_kv8_window.restype = ctypes.c_int
-    lib.sfa_decode_chunk_kv8_window.argtypes = [ctypes.POINTER(DecodeArgs), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                                ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]
-    lib.sfa_decode_varlen_kv8_window.restype = ctypes.c_int
-    lib.sfa_decode_varlen_kv8_window.argtypes = [ctypes.POINTER(DecodeArgs), ctypes.c_void_p, ctypes.c_void_p,
-                                                 ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
-                                                 ctypes.c_void_p]
-    lib.sfa_decode_window_sinks.restype = ctypes.c_int
-    lib.sfa_decode_window_sinks.argtypes = [ctypes.POINTER(DecodeArgs), ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
-    lib.sfa_decode_chunk_window_sinks.restype = ctypes.c_int
-    lib.sfa_decode_chunk_window_sinks.argtypes = [ctypes.POINTER(DecodeArgs), ctypes.c_void_p, ctypes.c_int,
-                                                  ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]
-    lib.sfa_decode_varlen_window_sinks.restype = ctypes.c_int
-    lib.sfa_decode_varlen_window_sinks.argtypes = [ctypes.POINTER(DecodeArgs), ctypes.c_void_p, ctypes.c_void_p,
-                                                   ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]
-    lib.sfa_decode_kv8_window_sinks.restype = ctypes.c_int
-    lib.sfa_decode_kv8_window_sinks.argtypes = [ctypes.POINTER(DecodeArgs), ctypes.c_void_p, ctypes.c_void_p,
-                                                ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
-    lib.sfa_decode_chunk_kv8_window_sinks.restype = ctypes.c_int
-    lib.sfa_decode_chunk_kv8_window_sinks.argtypes = [ctypes.POINTER(DecodeArgs), ctypes.c_void_p, ctypes.c_void_p,
-                                                      ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
-                                                      ctypes.c_void_p]
-    lib.sfa_decode_varlen_kv8_window_sinks.restype = ctypes.c_int
-    lib.sfa_decode_varlen_kv8_window_sinks.argtypes = [ctypes.POINTER(DecodeArgs), ctypes.c_void_p, ctypes.c_void_p,
-                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
-                                                       ctypes.c_int, ctypes.c_void_p]
     lib.sfa_prefill_fwd.restype = ctypes.c_int
     lib.sfa_prefill_fwd.argtypes = [ctypes.POINTER(PrefillArgs), ctypes.c_void_p]
     lib.sfa_prefill_window_fwd.restype = ctypes.c_int

@@ -128,34 +128,24 @@ static DecodeKernelParams decode_params(const sfa_decode_args *a, int hkv, int p
     return p;
 }
 
-// What sets the decode entry points apart in the argument checks they share
+// A decode entry point, described by data: one of three call shapes in one of six flavours ("Decode host
+// pipeline").  decode_call() below is everything the 18 of them do up to the launch.
+enum Shape { kSingle, kChunk, kVarlen };    // one token per sequence / `count` tokens per sequence / `count` packed tokens
 struct EntryPoint {
     const char *fn;             // names the entry point in the error text
-    const char *count_name;     // its token count: num_tokens per sequence, or, packed, total_tokens over all sequences
-    bool d256;                  // head_dim 256 is served
+    Shape shape;
+    bool window, kv8, sinks;    // a sliding window / e4m3 caches with scales / an attention sink per query head
+};
+// What differs by shape in the argument checks
+struct ShapeRules {
+    const char *count_name;     // the token count: num_tokens per sequence, or, packed, total_tokens over all sequences
+    bool d256;                  // head_dim 256 passes the shared checks (the single-token fp8 calls refuse it themselves)
     bool token_limits;          // the limits of the chunk kernels: batch_size, 32-bit lane offsets, count * group
     bool packed;                // the tokens of all sequences are packed: no batch stride
 };
-constexpr EntryPoint kDecode = {"sfa_decode", "num_tokens", true, false, false};
-constexpr EntryPoint kChunk = {"sfa_decode_chunk", "num_tokens", false, true, false};
-constexpr EntryPoint kVarlen = {"sfa_decode_varlen", "total_tokens", false, true, true};
-// (head_dim 256 passes the shared checks and is refused by sfa_decode_kv8 itself, with a message of its own)
-constexpr EntryPoint kKv8 = {"sfa_decode_kv8", "num_tokens", true, false, false};
-constexpr EntryPoint kWindow = {"sfa_decode_window", "num_tokens", true, false, false};
-// (head_dim 256: as kKv8)
-constexpr EntryPoint kKv8Window = {"sfa_decode_kv8_window", "num_tokens", true, false, false};
-constexpr EntryPoint kChunkWindow = {"sfa_decode_chunk_window", "num_tokens", false, true, false};
-constexpr EntryPoint kVarlenWindow = {"sfa_decode_varlen_window", "total_tokens", false, true, true};
-constexpr EntryPoint kWindowSinks = {"sfa_decode_window_sinks", "num_tokens", true, false, false};
-constexpr EntryPoint kChunkWindowSinks = {"sfa_decode_chunk_window_sinks", "num_tokens", false, true, false};
-constexpr EntryPoint kVarlenWindowSinks = {"sfa_decode_varlen_window_sinks", "total_tokens", false, true, true};
-constexpr EntryPoint kChunkKv8 = {"sfa_decode_chunk_kv8", "num_tokens", false, true, false};
-constexpr EntryPoint kVarlenKv8 = {"sfa_decode_varlen_kv8", "total_tokens", false, true, true};
-constexpr EntryPoint kChunkKv8Window = {"sfa_decode_chunk_kv8_window", "num_tokens", false, true, false};
-constexpr EntryPoint kVarlenKv8Window = {"sfa_decode_varlen_kv8_window", "total_tokens", false, true, true};
-constexpr EntryPoint kKv8WindowSinks = {"sfa_decode_kv8_window_sinks", "num_tokens", true, false, false};
-constexpr EntryPoint kChunkKv8WindowSinks = {"sfa_decode_chunk_kv8_window_sinks", "num_tokens", false, true, false};
-constexpr EntryPoint kVarlenKv8WindowSinks = {"sfa_decode_varlen_kv8_window_sinks", "total_tokens", false, true, true};
+constexpr ShapeRules kShapeRules[3] = {{"num_tokens", true, false, false},
+                                       {"num_tokens", false, true, false},
+                                       {"total_tokens", false, true, true}};
 
 // What the entry points check alike, before any HIP call, and what they derive on the way.  sfa_decode is the case of
 // one token per sequence (count = 1) with no token stride.
@@ -163,9 +153,10 @@ struct DecodeCall {
     int hkv, group, page_shift;
     long long tok, stride;      // elements between tokens / batches of qkv
 };
-static int validate_decode_call(const EntryPoint &e, const sfa_decode_args *a, int count, int64_t qkv_token_stride,
+static int validate_decode_call(const EntryPoint &ep, const sfa_decode_args *a, int count, int64_t qkv_token_stride,
                                 DecodeCall *out) {
-    const char *fn = e.fn;
+    const char *fn = ep.fn;
+    const ShapeRules &e = kShapeRules[ep.shape];
     if (!a) return fail(SFA_ERR_NULL_POINTER, "%s: args is NULL", fn);
     if (!a->qkv || !a->o || !a->seq_len || !a->k_cache_table || !a->v_cache_table)
         return fail(SFA_ERR_NULL_POINTER, "%s: qkv/o/seq_len/k_cache_table/v_cache_table must be non-NULL", fn);
@@ -252,6 +243,145 @@ static int check_workspace(const EntryPoint &e, const sfa_decode_args *a, size_t
         return fail(SFA_ERR_WORKSPACE_TOO_SMALL, "%s: workspace has %zu bytes, need %zu", e.fn, a->workspace_bytes, need);
     if ((uintptr_t)a->workspace & 255) return fail(SFA_ERR_BAD_SHAPE, "%s: workspace must be 256-byte aligned", e.fn);
     return SFA_OK;
+}
+
+// The rows a sequence can read under a sliding window, which the split count is chosen from instead of memory_max_len:
+// min(memory_max_len, window - 1 + count), count = the call's num_tokens / total_tokens, 1 for a single token (the first
+// token reads window rows, the last one ends count - 1 rows later).  A short window is not split into slivers, and the
+// rule never grows with that argument, so a workspace sized for the call without a window is never too small.
+static int window_rows(int M, int window, int count) {
+    const long long r = (long long)(window > 1 ? window : 1) - 1 + count;
+    return (int)(r < M ? (r > 1 ? r : 1) : M);
+}
+
+// (query rows per (batch, kv head) = num_tokens * group; bhr of them in all)
+static DecodeWorkspace chunk_workspace(int B, int hkv, long long rows, int S, int D) {
+    const size_t bhr = (size_t)B * hkv * rows;
+    return decode_workspace(0, bhr, bhr, S, D);
+}
+
+// (rows = total_tokens * group packed query rows per kv head)
+static DecodeWorkspace varlen_workspace(int B, int hkv, long long rows, int S, int D) {
+    const size_t hr = (size_t)hkv * rows;
+    return decode_workspace((size_t)varlen_plan_bound(B, rows), hr, hr, S, D);
+}
+
+// The arguments an entry point takes beside sfa_decode_args and the stream; one it does not take is 0 / nullptr
+// (count: 1 for a single token)
+struct DecodeExtras {
+    const float *k_scale, *v_scale, *sinks;
+    const void *cu_tokens;
+    int count;
+    int64_t tok_stride;
+    int window;
+};
+
+constexpr int kRun = 1;     // decode_call: launch (no status is positive)
+
+// Every decode entry point up to the launch: the argument checks, "nothing to do", the split count, the workspace and
+// the kernel parameters of the call's shape with their workspace pointers -- out->c.d for a single token, out->c for a
+// chunk, *out for varlen (what a shape does not have stays 0).  Returns kRun, SFA_OK (nothing to do) or an error.
+// The order of the checks is part of the C ABI's behaviour (an input may break several rules; DESIGN.md, "Decode host
+// pipeline", has the table).
+static int decode_call(const EntryPoint &e, const sfa_decode_args *a, const DecodeExtras &x, VarlenKernelParams *out) {
+    const bool single = e.shape == kSingle, varlen = e.shape == kVarlen;
+    const bool bad_scales = e.kv8 && (((uintptr_t)x.k_scale | (uintptr_t)x.v_scale) & 3);
+    const int count = x.count;
+    DecodeCall dc;
+    if (e.sinks && a && ((uintptr_t)x.sinks & 3)) return fail(SFA_ERR_BAD_SHAPE, "%s: sinks must be 4-byte aligned", e.fn);
+    // (the varlen fp8 calls check the scales first, the other fp8 calls after the shared checks)
+    if (varlen && bad_scales) return fail(SFA_ERR_BAD_SHAPE, "%s: k_scale / v_scale must be 4-byte aligned", e.fn);
+    if (varlen && a && !x.cu_tokens) return fail(SFA_ERR_NULL_POINTER, "%s: cu_tokens is NULL", e.fn);
+    if (const int rc = validate_decode_call(e, a, count, x.tok_stride, &dc)) return rc;
+    if (varlen && ((uintptr_t)x.cu_tokens & 3)) return fail(SFA_ERR_BAD_SHAPE, "%s: cu_tokens must be 4-byte aligned", e.fn);
+    if (single && e.kv8 && a->head_dim == 256)
+        return fail(SFA_ERR_UNSUPPORTED_HEAD_DIM,
+                    "%s: head_dim 256 is not supported over an fp8 cache yet (64 or 128; %s serves 256 on a 16-bit cache)",
+                    e.fn, e.window ? "sfa_decode_window" : "sfa_decode");
+    if (bad_scales) return fail(SFA_ERR_BAD_SHAPE, "%s: k_scale / v_scale must be 4-byte aligned", e.fn);
+    if (e.window && x.window < 1) return fail(SFA_ERR_BAD_SHAPE, "%s: window=%d must be >= 1", e.fn, x.window);
+    if (a->batch_size == 0 || count == 0) return SFA_OK;
+
+    const int B = a->batch_size, hkv = dc.hkv, D = a->head_dim;
+    const long long rows = (long long)count * dc.group;        // query rows per kv head (varlen: of all sequences)
+    const int bound = varlen ? varlen_plan_bound(B, rows) : 0;
+    const int M = e.window ? window_rows(a->memory_max_len, x.window, count) : a->memory_max_len;
+    // (single token: grouped queries launch one workgroup per kv head, so the split count follows the kv-head count)
+    const auto workspace = [&](int S) {
+        return single ? decode_workspace(0, 0, (size_t)B * a->num_heads, S, D)
+                      : varlen ? varlen_workspace(B, hkv, rows, S, D) : chunk_workspace(B, hkv, rows, S, D);
+    };
+    int S = a->num_splits > 0 ? a->num_splits
+                              : single ? auto_splits(B, hkv, M)
+                                       : varlen ? varlen_auto_splits(B, hkv, rows, M) : chunk_auto_splits(B, hkv, (int)rows, M);
+    // A caller that left the choice to the library may have sized its workspace for fewer splits than the library picks
+    // (sfa_decode_workspace_bytes(..., 0) knows the query-head count only; the windowed sizing functions may be given
+    // another window): take the largest split count the workspace holds rather than fail.  The single-token calls and
+    // every windowed call do; the chunk and varlen calls without a window do not.
+    if ((single || e.window) && a->num_splits <= 0 && a->workspace)
+        while (S > 1 && a->workspace_bytes < workspace(S).total) --S;
+    // the varlen attention kernel's 1-D grid: one workgroup per (plan slot, kv head, split)
+    if (varlen && (long long)bound * hkv * S > INT_MAX)
+        return fail(SFA_ERR_BAD_SHAPE,
+                    "%s: total_tokens=%d, batch_size=%d, num_heads_kv=%d and num_splits=%d need more than "
+                    "2^31 - 1 attention workgroups", e.fn, count, B, hkv, S);
+    const DecodeWorkspace w = workspace(S);
+    if (const int rc = check_workspace(e, a, w.total)) return rc;
+
+    VarlenKernelParams &p = *out;
+    memset(&p, 0, sizeof(p));
+    p.c.d = decode_params(a, hkv, dc.page_shift, S, varlen ? 0 : dc.stride);
+    char *ws = (char *)a->workspace;
+    p.c.d.part_o = (float *)(ws + w.part_o);
+    p.c.d.part_ml = (float2 *)(ws + w.part_ml);
+    if (single) return kRun;
+    p.c.q_rot = (uint16_t *)(ws + w.q_rot);
+    p.c.tok_stride = dc.tok;
+    p.c.G = dc.group;
+    if (varlen) {
+        p.cu_tokens = (const int32_t *)x.cu_tokens;
+        p.plan = (int2 *)(ws + w.plan);
+        p.rows = rows;
+        p.total = count;
+        p.bound = bound;
+    } else {
+        p.c.n = count;
+        p.c.R = (int)rows;
+    }
+    return kRun;
+}
+
+// The parameter struct P of a chunk or varlen flavour: `base`, the shape's parameters, and behind it the members the
+// flavour adds.  A _sinks call without sinks launches its twin, so both structs are filled here, from one source.
+template <class P, bool WINDOW, bool KV8, bool SINKS, class Base>
+static P flavour_params(const Base &base, const DecodeExtras &x) {
+    P p;
+    memset(&p, 0, sizeof(p));
+    p.base = base;
+    if constexpr (WINDOW) p.window = x.window;
+    if constexpr (KV8) p.k_scale = x.k_scale, p.v_scale = x.v_scale;
+    if constexpr (SINKS) p.sinks = x.sinks;
+    return p;
+}
+
+// The single-token flavours nest instead: kv8 = {d, scales}, window = {d or kv8, window}, sinks = {window, sinks}
+static Kv8KernelParams kv8_params(const DecodeKernelParams &d, const DecodeExtras &x) {
+    Kv8KernelParams p;
+    memset(&p, 0, sizeof(p));
+    p.d = d, p.k_scale = x.k_scale, p.v_scale = x.v_scale;
+    return p;
+}
+static WindowKernelParams window_params(const DecodeKernelParams &d, const DecodeExtras &x) {
+    WindowKernelParams p;
+    memset(&p, 0, sizeof(p));
+    p.d = d, p.window = x.window;
+    return p;
+}
+static Kv8WindowKernelParams kv8_window_params(const DecodeKernelParams &d, const DecodeExtras &x) {
+    Kv8WindowKernelParams p;
+    memset(&p, 0, sizeof(p));
+    p.base = kv8_params(d, x), p.window = x.window;
+    return p;
 }
 
 }  // namespace sfa
@@ -350,186 +480,230 @@ int sfa_decode_poll_status(const void *workspace, void *stream) {
     return SFA_OK;
 }
 
-int sfa_decode(const sfa_decode_args *a, void *stream) {
-    DecodeCall dc;
-    if (const int rc = validate_decode_call(kDecode, a, 1, 0, &dc)) return rc;
-    if (a->batch_size == 0) return SFA_OK;
-
-    const size_t bh = (size_t)a->batch_size * a->num_heads;
-    // grouped queries launch one workgroup per KV head: the split count follows the kv-head count
-    int S = a->num_splits > 0 ? a->num_splits : auto_splits(a->batch_size, dc.hkv, a->memory_max_len);
-    // A caller that left the choice to the library sized its workspace with sfa_decode_workspace_bytes(..., 0), which
-    // knows the query-head count only: with grouped queries the library's own choice can be larger than the one that
-    // size was computed for.  Take the largest split count the workspace holds rather than fail.
-    if (a->num_splits <= 0 && a->workspace)
-        while (S > 1 && a->workspace_bytes < decode_workspace(0, 0, bh, S, a->head_dim).total) --S;
-    const DecodeWorkspace w = decode_workspace(0, 0, bh, S, a->head_dim);
-    if (const int rc = check_workspace(kDecode, a, w.total)) return rc;
-
-    DecodeKernelParams p = decode_params(a, dc.hkv, dc.page_shift, S, dc.stride);
-    char *ws = (char *)a->workspace;
-    p.part_o = (float *)(ws + w.part_o);
-    p.part_ml = (float2 *)(ws + w.part_ml);
-    return launch_decode(p, a->dtype, a->head_dim, (hipStream_t)stream);
-}
-
-// sfa_decode with e4m3 caches: the workspace, the split count and the status word are sfa_decode's
-int sfa_decode_kv8(const sfa_decode_args *a, const float *k_scale, const float *v_scale, void *stream) {
-    DecodeCall dc;
-    if (const int rc = validate_decode_call(kKv8, a, 1, 0, &dc)) return rc;
-    if (a->head_dim == 256)
-        return fail(SFA_ERR_UNSUPPORTED_HEAD_DIM,
-                    "sfa_decode_kv8: head_dim 256 is not supported over an fp8 cache yet (64 or 128; sfa_decode serves "
-                    "256 on a 16-bit cache)");
-    if (((uintptr_t)k_scale | (uintptr_t)v_scale) & 3)
-        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_kv8: k_scale / v_scale must be 4-byte aligned");
-    if (a->batch_size == 0) return SFA_OK;
-
-    const size_t bh = (size_t)a->batch_size * a->num_heads;
-    // one workgroup per kv head: the split count follows the kv-head count, as in grouped sfa_decode, and a workspace
-    // sized by the query-head count gets the largest split count it holds
-    int S = a->num_splits > 0 ? a->num_splits : auto_splits(a->batch_size, dc.hkv, a->memory_max_len);
-    if (a->num_splits <= 0 && a->workspace)
-        while (S > 1 && a->workspace_bytes < decode_workspace(0, 0, bh, S, a->head_dim).total) --S;
-    const DecodeWorkspace w = decode_workspace(0, 0, bh, S, a->head_dim);
-    if (const int rc = check_workspace(kKv8, a, w.total)) return rc;
-
-    Kv8KernelParams p;
-    memset(&p, 0, sizeof(p));
-    p.d = decode_params(a, dc.hkv, dc.page_shift, S, dc.stride);
-    char *ws = (char *)a->workspace;
-    p.d.part_o = (float *)(ws + w.part_o);
-    p.d.part_ml = (float2 *)(ws + w.part_ml);
-    p.k_scale = k_scale;
-    p.v_scale = v_scale;
-    return launch_decode_kv8(p, a->dtype, a->head_dim, (hipStream_t)stream);
-}
-
-// sfa_decode with a sliding window.  The split count is sfa_decode's rule over the rows a sequence can read,
-// min(window, memory_max_len), by kv-head count: a short window is not split into slivers.
-static int window_auto_splits(int B, int hkv, int M, int window) {
-    return auto_splits(B, hkv, window < M ? (window > 1 ? window : 1) : M);
-}
-
+// The workspace sizes of the windowed calls: the split count, when the library picks it, is the twin's rule over
+// window_rows() instead of memory_max_len.
 size_t sfa_decode_window_workspace_bytes(int batch_size, int num_heads, int num_heads_kv, int head_dim,
                                          int memory_max_len, int window, int num_splits) {
     if (batch_size <= 0 || num_heads <= 0 || head_dim <= 0 || memory_max_len <= 0) return kStatusBytes;
     const int hkv = num_heads_kv > 0 ? num_heads_kv : num_heads;
-    const int S = num_splits > 0 ? num_splits : window_auto_splits(batch_size, hkv, memory_max_len, window);
+    const int S = num_splits > 0 ? num_splits : auto_splits(batch_size, hkv, window_rows(memory_max_len, window, 1));
     return sfa_decode_workspace_bytes(batch_size, num_heads, head_dim, memory_max_len, S);
 }
 
-// sfa_decode_window and its twin with attention sinks up to the launch: the checks, the split count, the workspace and
-// the kernel parameters.  *run = false: nothing to do
-static int window_call(const EntryPoint &e, const sfa_decode_args *a, int window, WindowKernelParams *out, bool *run) {
-    DecodeCall dc;
-    *run = false;
-    if (const int rc = validate_decode_call(e, a, 1, 0, &dc)) return rc;
-    if (window < 1) return fail(SFA_ERR_BAD_SHAPE, "%s: window=%d must be >= 1", e.fn, window);
-    if (a->batch_size == 0) return SFA_OK;
+size_t sfa_decode_chunk_workspace_bytes(int batch_size, int num_heads, int num_heads_kv, int head_dim,
+                                        int memory_max_len, int num_tokens, int num_splits) {
+    if (batch_size <= 0 || num_heads <= 0 || head_dim <= 0 || num_tokens <= 0) return kStatusBytes;
+    const int hkv = num_heads_kv > 0 ? num_heads_kv : num_heads;
+    const long long rows = (long long)num_tokens * (num_heads / hkv);
+    const int S = num_splits > 0 ? num_splits
+                                 : chunk_auto_splits(batch_size, hkv, (int)(rows < INT_MAX ? rows : INT_MAX), memory_max_len);
+    return chunk_workspace(batch_size, hkv, rows, S, head_dim).total;
+}
 
-    const size_t bh = (size_t)a->batch_size * a->num_heads;
-    // as in sfa_decode: a workspace sized for fewer splits than the library would pick gets the largest count it holds
-    int S = a->num_splits > 0 ? a->num_splits : window_auto_splits(a->batch_size, dc.hkv, a->memory_max_len, window);
-    if (a->num_splits <= 0 && a->workspace)
-        while (S > 1 && a->workspace_bytes < decode_workspace(0, 0, bh, S, a->head_dim).total) --S;
-    const DecodeWorkspace w = decode_workspace(0, 0, bh, S, a->head_dim);
-    if (const int rc = check_workspace(e, a, w.total)) return rc;
+size_t sfa_decode_chunk_window_workspace_bytes(int batch_size, int num_heads, int num_heads_kv, int head_dim,
+                                               int memory_max_len, int num_tokens, int window, int num_splits) {
+    return sfa_decode_chunk_workspace_bytes(batch_size, num_heads, num_heads_kv, head_dim,
+                                            window_rows(memory_max_len, window, num_tokens), num_tokens, num_splits);
+}
 
-    WindowKernelParams &p = *out;
-    p.d = decode_params(a, dc.hkv, dc.page_shift, S, dc.stride);
-    char *ws = (char *)a->workspace;
-    p.d.part_o = (float *)(ws + w.part_o);
-    p.d.part_ml = (float2 *)(ws + w.part_ml);
-    p.window = window;
-    *run = true;
-    return SFA_OK;
+size_t sfa_decode_varlen_workspace_bytes(int batch_size, int num_heads, int num_heads_kv, int head_dim,
+                                         int memory_max_len, int total_tokens, int num_splits) {
+    if (batch_size <= 0 || num_heads <= 0 || head_dim <= 0 || total_tokens <= 0) return kStatusBytes;
+    const int hkv = num_heads_kv > 0 ? num_heads_kv : num_heads;
+    const long long rows = (long long)total_tokens * (num_heads / hkv);
+    const int S = num_splits > 0 ? num_splits : varlen_auto_splits(batch_size, hkv, rows, memory_max_len);
+    return varlen_workspace(batch_size, hkv, rows, S, head_dim).total;
+}
+
+size_t sfa_decode_varlen_window_workspace_bytes(int batch_size, int num_heads, int num_heads_kv, int head_dim,
+                                                int memory_max_len, int total_tokens, int window, int num_splits) {
+    return sfa_decode_varlen_workspace_bytes(batch_size, num_heads, num_heads_kv, head_dim,
+                                             window_rows(memory_max_len, window, total_tokens), total_tokens, num_splits);
+}
+
+// The 18 decode entry points: describe the call, run decode_call(), fill the flavour's parameter struct and call its
+// launcher.  The fp8 calls keep the workspace, the split rule (tuned on 16-bit rows and not re-tuned for one-byte rows)
+// and the status word of their 16-bit twins.  A _sinks call with sinks == NULL is its twin, launch and all.
+
+
+int sfa_decode(const sfa_decode_args *a, void *stream) {
+    const DecodeExtras x = {nullptr, nullptr, nullptr, nullptr, 1, 0, 0};
+    VarlenKernelParams v;
+    if (const int rc = decode_call({"sfa_decode", kSingle, false, false, false}, a, x, &v); rc != kRun) return rc;
+    return launch_decode(v.c.d, a->dtype, a->head_dim, (hipStream_t)stream);
+}
+
+int sfa_decode_kv8(const sfa_decode_args *a, const float *k_scale, const float *v_scale, void *stream) {
+    const DecodeExtras x = {k_scale, v_scale, nullptr, nullptr, 1, 0, 0};
+    VarlenKernelParams v;
+    if (const int rc = decode_call({"sfa_decode_kv8", kSingle, false, true, false}, a, x, &v); rc != kRun) return rc;
+    return launch_decode_kv8(kv8_params(v.c.d, x), a->dtype, a->head_dim, (hipStream_t)stream);
 }
 
 int sfa_decode_window(const sfa_decode_args *a, int window, void *stream) {
-    WindowKernelParams p;
-    memset(&p, 0, sizeof(p));
-    bool run;
-    if (const int rc = window_call(kWindow, a, window, &p, &run)) return rc;
-    if (!run) return SFA_OK;
-    return launch_decode_window(p, a->dtype, a->head_dim, (hipStream_t)stream);
+    const DecodeExtras x = {nullptr, nullptr, nullptr, nullptr, 1, 0, window};
+    VarlenKernelParams v;
+    if (const int rc = decode_call({"sfa_decode_window", kSingle, true, false, false}, a, x, &v); rc != kRun) return rc;
+    return launch_decode_window(window_params(v.c.d, x), a->dtype, a->head_dim, (hipStream_t)stream);
 }
 
-// sfa_decode_window with an attention sink per query head.  sinks == NULL: the call is sfa_decode_window's, launch and all
 int sfa_decode_window_sinks(const sfa_decode_args *a, const float *sinks, int window, void *stream) {
+    const DecodeExtras x = {nullptr, nullptr, sinks, nullptr, 1, 0, window};
+    VarlenKernelParams v;
+    if (const int rc = decode_call({"sfa_decode_window_sinks", kSingle, true, false, true}, a, x, &v); rc != kRun) return rc;
     WindowSinksKernelParams p;
     memset(&p, 0, sizeof(p));
-    bool run;
-    if (a && ((uintptr_t)sinks & 3)) return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_window_sinks: sinks must be 4-byte aligned");
-    if (const int rc = window_call(kWindowSinks, a, window, &p.base, &run)) return rc;
-    if (!run) return SFA_OK;
-    if (!sinks) return launch_decode_window(p.base, a->dtype, a->head_dim, (hipStream_t)stream);
-    p.sinks = sinks;
-    return launch_decode_window_sinks(p, a->dtype, a->head_dim, (hipStream_t)stream);
-}
-
-// sfa_decode_kv8 with a sliding window: the checks of sfa_decode_kv8 and sfa_decode_window; the workspace, its split
-// rule and the status word are sfa_decode_window's.  This is the call and its twin with attention sinks up to the launch:
-// the checks, the split count, the workspace and the kernel parameters.  *run = false: nothing to do
-static int kv8_window_call(const EntryPoint &e, const sfa_decode_args *a, const float *k_scale, const float *v_scale,
-                           int window, Kv8WindowKernelParams *out, bool *run) {
-    DecodeCall dc;
-    *run = false;
-    if (const int rc = validate_decode_call(e, a, 1, 0, &dc)) return rc;
-    if (a->head_dim == 256)
-        return fail(SFA_ERR_UNSUPPORTED_HEAD_DIM,
-                    "%s: head_dim 256 is not supported over an fp8 cache yet (64 or 128; "
-                    "sfa_decode_window serves 256 on a 16-bit cache)", e.fn);
-    if (((uintptr_t)k_scale | (uintptr_t)v_scale) & 3)
-        return fail(SFA_ERR_BAD_SHAPE, "%s: k_scale / v_scale must be 4-byte aligned", e.fn);
-    if (window < 1) return fail(SFA_ERR_BAD_SHAPE, "%s: window=%d must be >= 1", e.fn, window);
-    if (a->batch_size == 0) return SFA_OK;
-
-    const size_t bh = (size_t)a->batch_size * a->num_heads;
-    // as in sfa_decode_window: a workspace sized for fewer splits than the library would pick gets the largest count it
-    // holds
-    int S = a->num_splits > 0 ? a->num_splits : window_auto_splits(a->batch_size, dc.hkv, a->memory_max_len, window);
-    if (a->num_splits <= 0 && a->workspace)
-        while (S > 1 && a->workspace_bytes < decode_workspace(0, 0, bh, S, a->head_dim).total) --S;
-    const DecodeWorkspace w = decode_workspace(0, 0, bh, S, a->head_dim);
-    if (const int rc = check_workspace(e, a, w.total)) return rc;
-
-    Kv8WindowKernelParams &p = *out;
-    p.base.d = decode_params(a, dc.hkv, dc.page_shift, S, dc.stride);
-    char *ws = (char *)a->workspace;
-    p.base.d.part_o = (float *)(ws + w.part_o);
-    p.base.d.part_ml = (float2 *)(ws + w.part_ml);
-    p.base.k_scale = k_scale;
-    p.base.v_scale = v_scale;
-    p.window = window;
-    *run = true;
-    return SFA_OK;
+    p.base = window_params(v.c.d, x), p.sinks = sinks;
+    return sinks ? launch_decode_window_sinks(p, a->dtype, a->head_dim, (hipStream_t)stream)
+                 : launch_decode_window(p.base, a->dtype, a->head_dim, (hipStream_t)stream);
 }
 
 int sfa_decode_kv8_window(const sfa_decode_args *a, const float *k_scale, const float *v_scale, int window,
                           void *stream) {
-    Kv8WindowKernelParams p;
-    memset(&p, 0, sizeof(p));
-    bool run;
-    if (const int rc = kv8_window_call(kKv8Window, a, k_scale, v_scale, window, &p, &run)) return rc;
-    if (!run) return SFA_OK;
-    return launch_decode_kv8_window(p, a->dtype, a->head_dim, (hipStream_t)stream);
+    const DecodeExtras x = {k_scale, v_scale, nullptr, nullptr, 1, 0, window};
+    VarlenKernelParams v;
+    if (const int rc = decode_call({"sfa_decode_kv8_window", kSingle, true, true, false}, a, x, &v); rc != kRun) return rc;
+    return launch_decode_kv8_window(kv8_window_params(v.c.d, x), a->dtype, a->head_dim, (hipStream_t)stream);
 }
 
-// sfa_decode_kv8_window with an attention sink per query head.  sinks == NULL: the call is sfa_decode_kv8_window's,
-// launch and all
 int sfa_decode_kv8_window_sinks(const sfa_decode_args *a, const float *k_scale, const float *v_scale, const float *sinks,
                                 int window, void *stream) {
+    const DecodeExtras x = {k_scale, v_scale, sinks, nullptr, 1, 0, window};
+    VarlenKernelParams v;
+    if (const int rc = decode_call({"sfa_decode_kv8_window_sinks", kSingle, true, true, true}, a, x, &v); rc != kRun)
+        return rc;
     Kv8WindowSinksKernelParams p;
     memset(&p, 0, sizeof(p));
-    bool run;
-    if (a && ((uintptr_t)sinks & 3))
-        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_kv8_window_sinks: sinks must be 4-byte aligned");
-    if (const int rc = kv8_window_call(kKv8WindowSinks, a, k_scale, v_scale, window, &p.base, &run)) return rc;
-    if (!run) return SFA_OK;
-    if (!sinks) return launch_decode_kv8_window(p.base, a->dtype, a->head_dim, (hipStream_t)stream);
-    p.sinks = sinks;
-    return launch_decode_kv8_window_sinks(p, a->dtype, a->head_dim, (hipStream_t)stream);
+    p.base = kv8_window_params(v.c.d, x), p.sinks = sinks;
+    return sinks ? launch_decode_kv8_window_sinks(p, a->dtype, a->head_dim, (hipStream_t)stream)
+                 : launch_decode_kv8_window(p.base, a->dtype, a->head_dim, (hipStream_t)stream);
+}
+
+int sfa_decode_chunk(const sfa_decode_args *a, int num_tokens, int64_t qkv_token_stride, void *stream) {
+    const DecodeExtras x = {nullptr, nullptr, nullptr, nullptr, num_tokens, qkv_token_stride, 0};
+    VarlenKernelParams v;
+    if (const int rc = decode_call({"sfa_decode_chunk", kChunk, false, false, false}, a, x, &v); rc != kRun) return rc;
+    return launch_decode_chunk(v.c, a->dtype, a->head_dim, (hipStream_t)stream);
+}
+
+int sfa_decode_chunk_kv8(const sfa_decode_args *a, const float *k_scale, const float *v_scale, int num_tokens,
+                         int64_t qkv_token_stride, void *stream) {
+    const DecodeExtras x = {k_scale, v_scale, nullptr, nullptr, num_tokens, qkv_token_stride, 0};
+    VarlenKernelParams v;
+    if (const int rc = decode_call({"sfa_decode_chunk_kv8", kChunk, false, true, false}, a, x, &v); rc != kRun) return rc;
+    return launch_decode_chunk_kv8(flavour_params<ChunkKv8KernelParams, false, true, false>(v.c, x), a->dtype,
+                                   a->head_dim, (hipStream_t)stream);
+}
+
+int sfa_decode_chunk_window(const sfa_decode_args *a, int num_tokens, int64_t qkv_token_stride, int window,
+                            void *stream) {
+    const DecodeExtras x = {nullptr, nullptr, nullptr, nullptr, num_tokens, qkv_token_stride, window};
+    VarlenKernelParams v;
+    if (const int rc = decode_call({"sfa_decode_chunk_window", kChunk, true, false, false}, a, x, &v); rc != kRun) return rc;
+    return launch_decode_chunk_window(flavour_params<ChunkWindowKernelParams, true, false, false>(v.c, x), a->dtype,
+                                      a->head_dim, (hipStream_t)stream);
+}
+
+int sfa_decode_chunk_window_sinks(const sfa_decode_args *a, const float *sinks, int num_tokens, int64_t qkv_token_stride,
+                                  int window, void *stream) {
+    const DecodeExtras x = {nullptr, nullptr, sinks, nullptr, num_tokens, qkv_token_stride, window};
+    VarlenKernelParams v;
+    if (const int rc = decode_call({"sfa_decode_chunk_window_sinks", kChunk, true, false, true}, a, x, &v); rc != kRun)
+        return rc;
+    if (!sinks)
+        return launch_decode_chunk_window(flavour_params<ChunkWindowKernelParams, true, false, false>(v.c, x), a->dtype,
+                                          a->head_dim, (hipStream_t)stream);
+    return launch_decode_chunk_window_sinks(flavour_params<ChunkWindowSinksKernelParams, true, false, true>(v.c, x),
+                                            a->dtype, a->head_dim, (hipStream_t)stream);
+}
+
+int sfa_decode_chunk_kv8_window(const sfa_decode_args *a, const float *k_scale, const float *v_scale, int num_tokens,
+                                int64_t qkv_token_stride, int window, void *stream) {
+    const DecodeExtras x = {k_scale, v_scale, nullptr, nullptr, num_tokens, qkv_token_stride, window};
+    VarlenKernelParams v;
+    if (const int rc = decode_call({"sfa_decode_chunk_kv8_window", kChunk, true, true, false}, a, x, &v); rc != kRun)
+        return rc;
+    return launch_decode_chunk_kv8_window(flavour_params<ChunkKv8WindowKernelParams, true, true, false>(v.c, x), a->dtype,
+                                          a->head_dim, (hipStream_t)stream);
+}
+
+int sfa_decode_chunk_kv8_window_sinks(const sfa_decode_args *a, const float *k_scale, const float *v_scale,
+                                      const float *sinks, int num_tokens, int64_t qkv_token_stride, int window,
+                                      void *stream) {
+    const DecodeExtras x = {k_scale, v_scale, sinks, nullptr, num_tokens, qkv_token_stride, window};
+    VarlenKernelParams v;
+    if (const int rc = decode_call({"sfa_decode_chunk_kv8_window_sinks", kChunk, true, true, true}, a, x, &v); rc != kRun)
+        return rc;
+    if (!sinks)
+        return launch_decode_chunk_kv8_window(flavour_params<ChunkKv8WindowKernelParams, true, true, false>(v.c, x),
+                                              a->dtype, a->head_dim, (hipStream_t)stream);
+    return launch_decode_chunk_kv8_window_sinks(flavour_params<ChunkKv8WindowSinksKernelParams, true, true, true>(v.c, x),
+                                                a->dtype, a->head_dim, (hipStream_t)stream);
+}
+
+int sfa_decode_varlen(const sfa_decode_args *a, const void *cu_tokens, int total_tokens, int64_t qkv_token_stride,
+                      void *stream) {
+    const DecodeExtras x = {nullptr, nullptr, nullptr, cu_tokens, total_tokens, qkv_token_stride, 0};
+    VarlenKernelParams v;
+    if (const int rc = decode_call({"sfa_decode_varlen", kVarlen, false, false, false}, a, x, &v); rc != kRun) return rc;
+    return launch_decode_varlen(v, a->dtype, a->head_dim, (hipStream_t)stream);
+}
+
+int sfa_decode_varlen_kv8(const sfa_decode_args *a, const float *k_scale, const float *v_scale, const void *cu_tokens,
+                          int total_tokens, int64_t qkv_token_stride, void *stream) {
+    const DecodeExtras x = {k_scale, v_scale, nullptr, cu_tokens, total_tokens, qkv_token_stride, 0};
+    VarlenKernelParams v;
+    if (const int rc = decode_call({"sfa_decode_varlen_kv8", kVarlen, false, true, false}, a, x, &v); rc != kRun) return rc;
+    return launch_decode_varlen_kv8(flavour_params<VarlenKv8KernelParams, false, true, false>(v, x), a->dtype,
+                                    a->head_dim, (hipStream_t)stream);
+}
+
+int sfa_decode_varlen_window(const sfa_decode_args *a, const void *cu_tokens, int total_tokens, int64_t qkv_token_stride,
+                             int window, void *stream) {
+    const DecodeExtras x = {nullptr, nullptr, nullptr, cu_tokens, total_tokens, qkv_token_stride, window};
+    VarlenKernelParams v;
+    if (const int rc = decode_call({"sfa_decode_varlen_window", kVarlen, true, false, false}, a, x, &v); rc != kRun)
+        return rc;
+    return launch_decode_varlen_window(flavour_params<VarlenWindowKernelParams, true, false, false>(v, x), a->dtype,
+                                       a->head_dim, (hipStream_t)stream);
+}
+
+int sfa_decode_varlen_window_sinks(const sfa_decode_args *a, const float *sinks, const void *cu_tokens, int total_tokens,
+                                   int64_t qkv_token_stride, int window, void *stream) {
+    const DecodeExtras x = {nullptr, nullptr, sinks, cu_tokens, total_tokens, qkv_token_stride, window};
+    VarlenKernelParams v;
+    if (const int rc = decode_call({"sfa_decode_varlen_window_sinks", kVarlen, true, false, true}, a, x, &v); rc != kRun)
+        return rc;
+    if (!sinks)
+        return launch_decode_varlen_window(flavour_params<VarlenWindowKernelParams, true, false, false>(v, x), a->dtype,
+                                           a->head_dim, (hipStream_t)stream);
+    return launch_decode_varlen_window_sinks(flavour_params<VarlenWindowSinksKernelParams, true, false, true>(v, x),
+                                             a->dtype, a->head_dim, (hipStream_t)stream);
+}
+
+int sfa_decode_varlen_kv8_window(const sfa_decode_args *a, const float *k_scale, const float *v_scale,
+                                 const void *cu_tokens, int total_tokens, int64_t qkv_token_stride, int window,
+                                 void *stream) {
+    const DecodeExtras x = {k_scale, v_scale, nullptr, cu_tokens, total_tokens, qkv_token_stride, window};
+    VarlenKernelParams v;
+    if (const int rc = decode_call({"sfa_decode_varlen_kv8_window", kVarlen, true, true, false}, a, x, &v); rc != kRun)
+        return rc;
+    return launch_decode_varlen_kv8_window(flavour_params<VarlenKv8WindowKernelParams, true, true, false>(v, x), a->dtype,
+                                           a->head_dim, (hipStream_t)stream);
+}
+
+int sfa_decode_varlen_kv8_window_sinks(const sfa_decode_args *a, const float *k_scale, const float *v_scale,
+                                       const float *sinks, const void *cu_tokens, int total_tokens,
+                                       int64_t qkv_token_stride, int window, void *stream) {
+    const DecodeExtras x = {k_scale, v_scale, sinks, cu_tokens, total_tokens, qkv_token_stride, window};
+    VarlenKernelParams v;
+    if (const int rc = decode_call({"sfa_decode_varlen_kv8_window_sinks", kVarlen, true, true, true}, a, x, &v); rc != kRun)
+        return rc;
+    if (!sinks)
+        return launch_decode_varlen_kv8_window(flavour_params<VarlenKv8WindowKernelParams, true, true, false>(v, x),
+                                               a->dtype, a->head_dim, (hipStream_t)stream);
+    return launch_decode_varlen_kv8_window_sinks(flavour_params<VarlenKv8WindowSinksKernelParams, true, true, true>(v, x),
+                                                 a->dtype, a->head_dim, (hipStream_t)stream);
 }
 
 int sfa_kv8_quantize(void *dst, const void *src, const float *scale, int64_t rows, int num_heads_kv, int head_dim,
@@ -551,388 +725,6 @@ int sfa_kv8_quantize(void *dst, const void *src, const float *scale, int64_t row
     if ((uintptr_t)scale & 3) return fail(SFA_ERR_BAD_SHAPE, "sfa_kv8_quantize: scale must be 4-byte aligned");
     return launch_kv8_quantize(dst, src, scale, rows, num_heads_kv, head_dim, src_row_stride, src_head_stride,
                                dst_row_stride, dst_head_stride, dtype, (hipStream_t)stream);
-}
-
-// (query rows per (batch, kv head) = num_tokens * group; bhr of them in all)
-static DecodeWorkspace chunk_workspace(int B, int hkv, long long rows, int S, int D) {
-    const size_t bhr = (size_t)B * hkv * rows;
-    return decode_workspace(0, bhr, bhr, S, D);
-}
-
-size_t sfa_decode_chunk_workspace_bytes(int batch_size, int num_heads, int num_heads_kv, int head_dim,
-                                        int memory_max_len, int num_tokens, int num_splits) {
-    if (batch_size <= 0 || num_heads <= 0 || head_dim <= 0 || num_tokens <= 0) return kStatusBytes;
-    const int hkv = num_heads_kv > 0 ? num_heads_kv : num_heads;
-    const long long rows = (long long)num_tokens * (num_heads / hkv);
-    const int S = num_splits > 0 ? num_splits
-                                 : chunk_auto_splits(batch_size, hkv, (int)(rows < INT_MAX ? rows : INT_MAX), memory_max_len);
-    return chunk_workspace(batch_size, hkv, rows, S, head_dim).total;
-}
-
-// The kernel parameters of a validated chunk call with S splits and its workspace laid out as w
-static ChunkKernelParams chunk_params(const sfa_decode_args *a, const DecodeCall &dc, int num_tokens, int S,
-                                      const DecodeWorkspace &w) {
-    ChunkKernelParams p;
-    memset(&p, 0, sizeof(p));
-    p.d = decode_params(a, dc.hkv, dc.page_shift, S, dc.stride);
-    char *ws = (char *)a->workspace;
-    p.q_rot = (uint16_t *)(ws + w.q_rot);
-    p.d.part_o = (float *)(ws + w.part_o);
-    p.d.part_ml = (float2 *)(ws + w.part_ml);
-    p.tok_stride = dc.tok;
-    p.n = num_tokens;
-    p.G = dc.group;
-    p.R = num_tokens * dc.group;
-    return p;
-}
-
-int sfa_decode_chunk(const sfa_decode_args *a, int num_tokens, int64_t qkv_token_stride, void *stream) {
-    DecodeCall dc;
-    if (const int rc = validate_decode_call(kChunk, a, num_tokens, qkv_token_stride, &dc)) return rc;
-    if (a->batch_size == 0 || num_tokens == 0) return SFA_OK;
-
-    const int rows = num_tokens * dc.group;
-    const int S = a->num_splits > 0 ? a->num_splits : chunk_auto_splits(a->batch_size, dc.hkv, rows, a->memory_max_len);
-    const DecodeWorkspace w = chunk_workspace(a->batch_size, dc.hkv, rows, S, a->head_dim);
-    if (const int rc = check_workspace(kChunk, a, w.total)) return rc;
-    return launch_decode_chunk(chunk_params(a, dc, num_tokens, S, w), a->dtype, a->head_dim, (hipStream_t)stream);
-}
-
-// The sliding-window twins of the chunk and varlen calls.  When the library picks the split count it is the twin's rule
-// over the rows a sequence can read instead of memory_max_len: min(memory_max_len, window - 1 + count), count = the
-// call's num_tokens / total_tokens (the first token reads window rows, the last one ends count - 1 rows later).  The
-// rule never grows with that argument, so a workspace sized for the call without a window is never too small.
-static int window_rows(int M, int window, int count) {
-    const long long r = (long long)(window > 1 ? window : 1) - 1 + count;
-    return (int)(r < M ? (r > 1 ? r : 1) : M);
-}
-
-size_t sfa_decode_chunk_window_workspace_bytes(int batch_size, int num_heads, int num_heads_kv, int head_dim,
-                                               int memory_max_len, int num_tokens, int window, int num_splits) {
-    return sfa_decode_chunk_workspace_bytes(batch_size, num_heads, num_heads_kv, head_dim,
-                                            window_rows(memory_max_len, window, num_tokens), num_tokens, num_splits);
-}
-
-// sfa_decode_chunk_window and its twin with attention sinks up to the launch.  *run = false: nothing to do
-static int chunk_window_call(const EntryPoint &e, const sfa_decode_args *a, int num_tokens, int64_t qkv_token_stride,
-                             int window, ChunkKernelParams *out, bool *run) {
-    DecodeCall dc;
-    *run = false;
-    if (const int rc = validate_decode_call(e, a, num_tokens, qkv_token_stride, &dc)) return rc;
-    if (window < 1) return fail(SFA_ERR_BAD_SHAPE, "%s: window=%d must be >= 1", e.fn, window);
-    if (a->batch_size == 0 || num_tokens == 0) return SFA_OK;
-
-    const int rows = num_tokens * dc.group;
-    int S = a->num_splits > 0 ? a->num_splits
-                              : chunk_auto_splits(a->batch_size, dc.hkv, rows, window_rows(a->memory_max_len, window, num_tokens));
-    // as in sfa_decode: a workspace sized for fewer splits than the library would pick gets the largest count it holds
-    if (a->num_splits <= 0 && a->workspace)
-        while (S > 1 && a->workspace_bytes < chunk_workspace(a->batch_size, dc.hkv, rows, S, a->head_dim).total) --S;
-    const DecodeWorkspace w = chunk_workspace(a->batch_size, dc.hkv, rows, S, a->head_dim);
-    if (const int rc = check_workspace(e, a, w.total)) return rc;
-    *out = chunk_params(a, dc, num_tokens, S, w);
-    *run = true;
-    return SFA_OK;
-}
-
-int sfa_decode_chunk_window(const sfa_decode_args *a, int num_tokens, int64_t qkv_token_stride, int window,
-                            void *stream) {
-    ChunkWindowKernelParams p;
-    memset(&p, 0, sizeof(p));
-    bool run;
-    if (const int rc = chunk_window_call(kChunkWindow, a, num_tokens, qkv_token_stride, window, &p.base, &run)) return rc;
-    if (!run) return SFA_OK;
-    p.window = window;
-    return launch_decode_chunk_window(p, a->dtype, a->head_dim, (hipStream_t)stream);
-}
-
-// sfa_decode_chunk_window with an attention sink per query head.  sinks == NULL: the call is sfa_decode_chunk_window's
-int sfa_decode_chunk_window_sinks(const sfa_decode_args *a, const float *sinks, int num_tokens, int64_t qkv_token_stride,
-                                  int window, void *stream) {
-    ChunkWindowSinksKernelParams p;
-    memset(&p, 0, sizeof(p));
-    bool run;
-    if (a && ((uintptr_t)sinks & 3)) return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk_window_sinks: sinks must be 4-byte aligned");
-    if (const int rc = chunk_window_call(kChunkWindowSinks, a, num_tokens, qkv_token_stride, window, &p.base, &run))
-        return rc;
-    if (!run) return SFA_OK;
-    p.window = window;
-    p.sinks = sinks;
-    if (!sinks) {
-        ChunkWindowKernelParams wp;
-        memset(&wp, 0, sizeof(wp));
-        wp.base = p.base;
-        wp.window = window;
-        return launch_decode_chunk_window(wp, a->dtype, a->head_dim, (hipStream_t)stream);
-    }
-    return launch_decode_chunk_window_sinks(p, a->dtype, a->head_dim, (hipStream_t)stream);
-}
-
-// sfa_decode_chunk over e4m3 caches: the checks of sfa_decode_chunk and the scale check of sfa_decode_kv8; the workspace,
-// its split rule (tuned on 16-bit rows and not re-tuned for one-byte rows) and the status word are sfa_decode_chunk's
-int sfa_decode_chunk_kv8(const sfa_decode_args *a, const float *k_scale, const float *v_scale, int num_tokens,
-                         int64_t qkv_token_stride, void *stream) {
-    DecodeCall dc;
-    if (const int rc = validate_decode_call(kChunkKv8, a, num_tokens, qkv_token_stride, &dc)) return rc;
-    if (((uintptr_t)k_scale | (uintptr_t)v_scale) & 3)
-        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk_kv8: k_scale / v_scale must be 4-byte aligned");
-    if (a->batch_size == 0 || num_tokens == 0) return SFA_OK;
-
-    const int rows = num_tokens * dc.group;
-    const int S = a->num_splits > 0 ? a->num_splits : chunk_auto_splits(a->batch_size, dc.hkv, rows, a->memory_max_len);
-    const DecodeWorkspace w = chunk_workspace(a->batch_size, dc.hkv, rows, S, a->head_dim);
-    if (const int rc = check_workspace(kChunkKv8, a, w.total)) return rc;
-
-    ChunkKv8KernelParams p;
-    memset(&p, 0, sizeof(p));
-    p.base = chunk_params(a, dc, num_tokens, S, w);
-    p.k_scale = k_scale;
-    p.v_scale = v_scale;
-    return launch_decode_chunk_kv8(p, a->dtype, a->head_dim, (hipStream_t)stream);
-}
-
-// (rows = total_tokens * group packed query rows per kv head)
-static DecodeWorkspace varlen_workspace(int B, int hkv, long long rows, int S, int D) {
-    const size_t hr = (size_t)hkv * rows;
-    return decode_workspace((size_t)varlen_plan_bound(B, rows), hr, hr, S, D);
-}
-
-size_t sfa_decode_varlen_workspace_bytes(int batch_size, int num_heads, int num_heads_kv, int head_dim,
-                                         int memory_max_len, int total_tokens, int num_splits) {
-    if (batch_size <= 0 || num_heads <= 0 || head_dim <= 0 || total_tokens <= 0) return kStatusBytes;
-    const int hkv = num_heads_kv > 0 ? num_heads_kv : num_heads;
-    const long long rows = (long long)total_tokens * (num_heads / hkv);
-    const int S = num_splits > 0 ? num_splits : varlen_auto_splits(batch_size, hkv, rows, memory_max_len);
-    return varlen_workspace(batch_size, hkv, rows, S, head_dim).total;
-}
-
-// sfa_decode_varlen and its sliding-window twin (windowed) up to the launch: the checks, the split count, the
-// workspace and the kernel parameters
-static int varlen_call(const EntryPoint &e, const sfa_decode_args *a, const void *cu_tokens, int total_tokens,
-                       int64_t qkv_token_stride, bool windowed, int window, VarlenKernelParams *out) {
-    DecodeCall dc;
-    if (a && !cu_tokens) return fail(SFA_ERR_NULL_POINTER, "%s: cu_tokens is NULL", e.fn);
-    if (const int rc = validate_decode_call(e, a, total_tokens, qkv_token_stride, &dc)) return rc;
-    if ((uintptr_t)cu_tokens & 3) return fail(SFA_ERR_BAD_SHAPE, "%s: cu_tokens must be 4-byte aligned", e.fn);
-    if (windowed && window < 1) return fail(SFA_ERR_BAD_SHAPE, "%s: window=%d must be >= 1", e.fn, window);
-    const long long rows = (long long)total_tokens * dc.group;
-    if (a->batch_size == 0 || total_tokens == 0) return SFA_OK;
-
-    const int hkv = dc.hkv, bound = varlen_plan_bound(a->batch_size, rows);
-    const int M = windowed ? window_rows(a->memory_max_len, window, total_tokens) : a->memory_max_len;
-    int S = a->num_splits > 0 ? a->num_splits : varlen_auto_splits(a->batch_size, hkv, rows, M);
-    // (window) as in sfa_decode: a workspace sized for fewer splits than the library would pick gets the largest count it
-    // holds
-    if (windowed && a->num_splits <= 0 && a->workspace)
-        while (S > 1 && a->workspace_bytes < varlen_workspace(a->batch_size, hkv, rows, S, a->head_dim).total) --S;
-    // the attention kernel's 1-D grid: one workgroup per (plan slot, kv head, split)
-    if ((long long)bound * hkv * S > INT_MAX)
-        return fail(SFA_ERR_BAD_SHAPE,
-                    "%s: total_tokens=%d, batch_size=%d, num_heads_kv=%d and num_splits=%d need more than "
-                    "2^31 - 1 attention workgroups", e.fn, total_tokens, a->batch_size, hkv, S);
-    const DecodeWorkspace w = varlen_workspace(a->batch_size, hkv, rows, S, a->head_dim);
-    if (const int rc = check_workspace(e, a, w.total)) return rc;
-
-    VarlenKernelParams &p = *out;
-    p.c.d = decode_params(a, hkv, dc.page_shift, S, 0);
-    p.c.tok_stride = dc.tok;
-    p.c.G = dc.group;
-    p.cu_tokens = (const int32_t *)cu_tokens;
-    p.rows = rows;
-    p.total = total_tokens;
-    p.bound = bound;
-    char *ws = (char *)a->workspace;
-    p.plan = (int2 *)(ws + w.plan);
-    p.c.q_rot = (uint16_t *)(ws + w.q_rot);
-    p.c.d.part_o = (float *)(ws + w.part_o);
-    p.c.d.part_ml = (float2 *)(ws + w.part_ml);
-    return SFA_OK;
-}
-
-int sfa_decode_varlen(const sfa_decode_args *a, const void *cu_tokens, int total_tokens, int64_t qkv_token_stride,
-                      void *stream) {
-    VarlenKernelParams p;
-    memset(&p, 0, sizeof(p));
-    if (const int rc = varlen_call(kVarlen, a, cu_tokens, total_tokens, qkv_token_stride, false, 0, &p)) return rc;
-    if (!p.cu_tokens) return SFA_OK;            // nothing to do
-    return launch_decode_varlen(p, a->dtype, a->head_dim, (hipStream_t)stream);
-}
-
-size_t sfa_decode_varlen_window_workspace_bytes(int batch_size, int num_heads, int num_heads_kv, int head_dim,
-                                                int memory_max_len, int total_tokens, int window, int num_splits) {
-    return sfa_decode_varlen_workspace_bytes(batch_size, num_heads, num_heads_kv, head_dim,
-                                             window_rows(memory_max_len, window, total_tokens), total_tokens, num_splits);
-}
-
-int sfa_decode_varlen_window(const sfa_decode_args *a, const void *cu_tokens, int total_tokens, int64_t qkv_token_stride,
-                             int window, void *stream) {
-    VarlenWindowKernelParams p;
-    memset(&p, 0, sizeof(p));
-    if (const int rc = varlen_call(kVarlenWindow, a, cu_tokens, total_tokens, qkv_token_stride, true, window, &p.base))
-        return rc;
-    if (!p.base.cu_tokens) return SFA_OK;       // nothing to do
-    p.window = window;
-    return launch_decode_varlen_window(p, a->dtype, a->head_dim, (hipStream_t)stream);
-}
-
-// sfa_decode_varlen_window with an attention sink per query head.  sinks == NULL: the call is sfa_decode_varlen_window's
-int sfa_decode_varlen_window_sinks(const sfa_decode_args *a, const float *sinks, const void *cu_tokens, int total_tokens,
-                                   int64_t qkv_token_stride, int window, void *stream) {
-    VarlenWindowSinksKernelParams p;
-    memset(&p, 0, sizeof(p));
-    // (before varlen_call, whose last check is the workspace)
-    if (a && ((uintptr_t)sinks & 3)) return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_varlen_window_sinks: sinks must be 4-byte aligned");
-    if (const int rc = varlen_call(kVarlenWindowSinks, a, cu_tokens, total_tokens, qkv_token_stride, true, window, &p.base))
-        return rc;
-    if (!p.base.cu_tokens) return SFA_OK;       // nothing to do
-    p.window = window;
-    p.sinks = sinks;
-    if (!sinks) {
-        VarlenWindowKernelParams wp;
-        memset(&wp, 0, sizeof(wp));
-        wp.base = p.base;
-        wp.window = window;
-        return launch_decode_varlen_window(wp, a->dtype, a->head_dim, (hipStream_t)stream);
-    }
-    return launch_decode_varlen_window_sinks(p, a->dtype, a->head_dim, (hipStream_t)stream);
-}
-
-// sfa_decode_varlen over e4m3 caches: as sfa_decode_chunk_kv8 is to sfa_decode_chunk
-int sfa_decode_varlen_kv8(const sfa_decode_args *a, const float *k_scale, const float *v_scale, const void *cu_tokens,
-                          int total_tokens, int64_t qkv_token_stride, void *stream) {
-    VarlenKv8KernelParams p;
-    memset(&p, 0, sizeof(p));
-    // (before varlen_call, whose last check is the workspace: as in sfa_decode_kv8 the scales are checked before it)
-    if (((uintptr_t)k_scale | (uintptr_t)v_scale) & 3)
-        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_varlen_kv8: k_scale / v_scale must be 4-byte aligned");
-    if (const int rc = varlen_call(kVarlenKv8, a, cu_tokens, total_tokens, qkv_token_stride, false, 0, &p.base)) return rc;
-    if (!p.base.cu_tokens) return SFA_OK;       // nothing to do
-    p.k_scale = k_scale;
-    p.v_scale = v_scale;
-    return launch_decode_varlen_kv8(p, a->dtype, a->head_dim, (hipStream_t)stream);
-}
-
-// sfa_decode_chunk_kv8 with a sliding window: the checks of sfa_decode_chunk_kv8 and sfa_decode_chunk_window, in the fp8
-// twin's order (scales before the workspace); the workspace, its split rule and the status word are
-// sfa_decode_chunk_window's.  This is the call and its twin with attention sinks up to the launch; *run = false: nothing
-// to do
-static int chunk_kv8_window_call(const EntryPoint &e, const sfa_decode_args *a, const float *k_scale, const float *v_scale,
-                                 int num_tokens, int64_t qkv_token_stride, int window, ChunkKv8WindowKernelParams *out,
-                                 bool *run) {
-    DecodeCall dc;
-    *run = false;
-    if (const int rc = validate_decode_call(e, a, num_tokens, qkv_token_stride, &dc)) return rc;
-    if (((uintptr_t)k_scale | (uintptr_t)v_scale) & 3)
-        return fail(SFA_ERR_BAD_SHAPE, "%s: k_scale / v_scale must be 4-byte aligned", e.fn);
-    if (window < 1) return fail(SFA_ERR_BAD_SHAPE, "%s: window=%d must be >= 1", e.fn, window);
-    if (a->batch_size == 0 || num_tokens == 0) return SFA_OK;
-
-    const int rows = num_tokens * dc.group;
-    int S = a->num_splits > 0 ? a->num_splits
-                              : chunk_auto_splits(a->batch_size, dc.hkv, rows, window_rows(a->memory_max_len, window, num_tokens));
-    // as in sfa_decode_chunk_window: a workspace sized for fewer splits than the library would pick gets the largest count
-    // it holds
-    if (a->num_splits <= 0 && a->workspace)
-        while (S > 1 && a->workspace_bytes < chunk_workspace(a->batch_size, dc.hkv, rows, S, a->head_dim).total) --S;
-    const DecodeWorkspace w = chunk_workspace(a->batch_size, dc.hkv, rows, S, a->head_dim);
-    if (const int rc = check_workspace(e, a, w.total)) return rc;
-
-    ChunkKv8WindowKernelParams &p = *out;
-    p.base = chunk_params(a, dc, num_tokens, S, w);
-    p.window = window;
-    p.k_scale = k_scale;
-    p.v_scale = v_scale;
-    *run = true;
-    return SFA_OK;
-}
-
-int sfa_decode_chunk_kv8_window(const sfa_decode_args *a, const float *k_scale, const float *v_scale, int num_tokens,
-                                int64_t qkv_token_stride, int window, void *stream) {
-    ChunkKv8WindowKernelParams p;
-    memset(&p, 0, sizeof(p));
-    bool run;
-    if (const int rc = chunk_kv8_window_call(kChunkKv8Window, a, k_scale, v_scale, num_tokens, qkv_token_stride, window,
-                                             &p, &run))
-        return rc;
-    if (!run) return SFA_OK;
-    return launch_decode_chunk_kv8_window(p, a->dtype, a->head_dim, (hipStream_t)stream);
-}
-
-// sfa_decode_chunk_kv8_window with an attention sink per query head.  sinks == NULL: the call is
-// sfa_decode_chunk_kv8_window's, launch and all
-int sfa_decode_chunk_kv8_window_sinks(const sfa_decode_args *a, const float *k_scale, const float *v_scale,
-                                      const float *sinks, int num_tokens, int64_t qkv_token_stride, int window,
-                                      void *stream) {
-    ChunkKv8WindowKernelParams wp;
-    memset(&wp, 0, sizeof(wp));
-    bool run;
-    if (a && ((uintptr_t)sinks & 3))
-        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_chunk_kv8_window_sinks: sinks must be 4-byte aligned");
-    if (const int rc = chunk_kv8_window_call(kChunkKv8WindowSinks, a, k_scale, v_scale, num_tokens, qkv_token_stride,
-                                             window, &wp, &run))
-        return rc;
-    if (!run) return SFA_OK;
-    if (!sinks) return launch_decode_chunk_kv8_window(wp, a->dtype, a->head_dim, (hipStream_t)stream);
-    ChunkKv8WindowSinksKernelParams p;
-    memset(&p, 0, sizeof(p));
-    p.base = wp.base;
-    p.window = wp.window;
-    p.k_scale = wp.k_scale;
-    p.v_scale = wp.v_scale;
-    p.sinks = sinks;
-    return launch_decode_chunk_kv8_window_sinks(p, a->dtype, a->head_dim, (hipStream_t)stream);
-}
-
-// sfa_decode_varlen_kv8 with a sliding window: as sfa_decode_chunk_kv8_window is to sfa_decode_chunk_kv8.  This is the
-// call and its twin with attention sinks up to the launch; out->base.cu_tokens stays NULL: nothing to do
-static int varlen_kv8_window_call(const EntryPoint &e, const sfa_decode_args *a, const float *k_scale, const float *v_scale,
-                                  const void *cu_tokens, int total_tokens, int64_t qkv_token_stride, int window,
-                                  VarlenKv8WindowKernelParams *out) {
-    VarlenKv8WindowKernelParams &p = *out;
-    // (before varlen_call, whose last check is the workspace: as in sfa_decode_varlen_kv8)
-    if (((uintptr_t)k_scale | (uintptr_t)v_scale) & 3)
-        return fail(SFA_ERR_BAD_SHAPE, "%s: k_scale / v_scale must be 4-byte aligned", e.fn);
-    if (const int rc = varlen_call(e, a, cu_tokens, total_tokens, qkv_token_stride, true, window, &p.base)) return rc;
-    p.window = window;
-    p.k_scale = k_scale;
-    p.v_scale = v_scale;
-    return SFA_OK;
-}
-
-int sfa_decode_varlen_kv8_window(const sfa_decode_args *a, const float *k_scale, const float *v_scale,
-                                 const void *cu_tokens, int total_tokens, int64_t qkv_token_stride, int window,
-                                 void *stream) {
-    VarlenKv8WindowKernelParams p;
-    memset(&p, 0, sizeof(p));
-    if (const int rc = varlen_kv8_window_call(kVarlenKv8Window, a, k_scale, v_scale, cu_tokens, total_tokens,
-                                              qkv_token_stride, window, &p))
-        return rc;
-    if (!p.base.cu_tokens) return SFA_OK;       // nothing to do
-    return launch_decode_varlen_kv8_window(p, a->dtype, a->head_dim, (hipStream_t)stream);
-}
-
-// sfa_decode_varlen_kv8_window with an attention sink per query head.  sinks == NULL: the call is
-// sfa_decode_varlen_kv8_window's, launch and all
-int sfa_decode_varlen_kv8_window_sinks(const sfa_decode_args *a, const float *k_scale, const float *v_scale,
-                                       const float *sinks, const void *cu_tokens, int total_tokens,
-                                       int64_t qkv_token_stride, int window, void *stream) {
-    VarlenKv8WindowKernelParams wp;
-    memset(&wp, 0, sizeof(wp));
-    if (a && ((uintptr_t)sinks & 3))
-        return fail(SFA_ERR_BAD_SHAPE, "sfa_decode_varlen_kv8_window_sinks: sinks must be 4-byte aligned");
-    if (const int rc = varlen_kv8_window_call(kVarlenKv8WindowSinks, a, k_scale, v_scale, cu_tokens, total_tokens,
-                                              qkv_token_stride, window, &wp))
-        return rc;
-    if (!wp.base.cu_tokens) return SFA_OK;      // nothing to do
-    if (!sinks) return launch_decode_varlen_kv8_window(wp, a->dtype, a->head_dim, (hipStream_t)stream);
-    VarlenKv8WindowSinksKernelParams p;
-    memset(&p, 0, sizeof(p));
-    p.base = wp.base;
-    p.window = wp.window;
-    p.k_scale = wp.k_scale;
-    p.v_scale = wp.v_scale;
-    p.sinks = sinks;
-    return launch_decode_varlen_kv8_window_sinks(p, a->dtype, a->head_dim, (hipStream_t)stream);
 }
 
 }  // extern "C"

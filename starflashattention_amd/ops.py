@@ -162,16 +162,100 @@ def _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_
     return a, B, H, Hkv, D, M
 
 
-def _call_decode(dev, a, stride, num_splits, ws, call):
+def _call_decode(dev, a, stride, num_splits, ws, fn, extra):
     """What the decode operators end in: the batch stride, the split count and the workspace go into `a`,
-    call(args, stream) makes the C-ABI call and, with sync checks on, the status is polled."""
+    fn(args, *extra, stream) makes the C-ABI call and, with sync checks on, the status is polled."""
     a.stride = stride
     a.num_splits = num_splits
     a.workspace = ws.data_ptr()
     a.workspace_bytes = ws.numel()
-    _lib.check(call(ctypes.byref(a), _stream_ptr(dev)))
+    _lib.check(fn(ctypes.byref(a), *extra, _stream_ptr(dev)))
     if _sync_checks:
         check_decode_status(dev)
+
+
+def _kv8_scale(t, name, Hkv, dev):
+    if t is None:
+        return None
+    _check_gpu_tensor(t, name, torch.float32, (Hkv,), dev)
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def _window_int(window):
+    W = int(window)
+    _require(-2 ** 31 <= W < 2 ** 31, f"window={window} does not fit an int")
+    return W
+
+
+def _sinks_ptr(sinks, H, dev):
+    """sinks: None (NULL: the call is its _window twin) or a float32 [num_heads] device tensor, one logit per query head"""
+    if sinks is None:
+        return None
+    _check_gpu_tensor(sinks, "sinks", torch.float32, (H,), dev)
+    return ctypes.c_void_p(sinks.data_ptr())
+
+
+def _decode_op(shape, flavour, qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+               memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length, num_layer, idx_layer,
+               num_splits, rotary_cos_table, rotary_sin_table, softmax_scale, kv_layout, block_table, num_heads_kv,
+               cu_tokens=None, window=None, sinks=None, k_scale=None, v_scale=None, sized_by_query_heads=False):
+    """The body of the 18 flash_decode* operators: the C call sfa_decode<shape><flavour>, shape "" / "_chunk" / "_varlen",
+    flavour "" / "_window" / "_window_sinks" / "_kv8" / "_kv8_window" / "_kv8_window_sinks".  The C calls take, between
+    args and the stream, [k_scale, v_scale], [sinks], [cu_tokens], [count, token stride], [window] (as _lib.load() declares
+    them); the operators check their arguments in the order window, scales, sinks, cu_tokens.  Returns `o`."""
+    lib = _lib.load()
+    windowed, kv8 = "_window" in flavour, "_kv8" in flavour
+    tokens = packed = None
+    if shape == "_chunk":
+        _require(isinstance(qkv, torch.Tensor) and qkv.dim() in (4, 5),
+                 f"qkv must be [B, n, 3, H, D] or [B, n, H + 2*Hkv, D] (got {tuple(getattr(qkv, 'shape', ()))})")
+        tokens = count = int(qkv.shape[1])
+    elif shape:
+        _require(isinstance(qkv, torch.Tensor) and qkv.dim() in (3, 4),
+                 f"qkv must be [T, 3, H, D] or [T, H + 2*Hkv, D] (got {tuple(getattr(qkv, 'shape', ()))})")
+        packed = count = int(qkv.shape[0])
+    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
+                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
+                                      kv_layout, block_table, num_heads_kv, tokens, packed, kv8)
+    dev = qkv.device
+    extra = []
+    if windowed:
+        W = _window_int(window)
+    if kv8:
+        extra += [_kv8_scale(k_scale, "k_scale", Hkv, dev), _kv8_scale(v_scale, "v_scale", Hkv, dev)]
+    if "_sinks" in flavour:
+        extra.append(_sinks_ptr(sinks, H, dev))
+    if packed is not None:
+        _check_gpu_tensor(cu_tokens, "cu_tokens", torch.int32, (B + 1,), dev)
+        extra.append(ctypes.c_void_p(cu_tokens.data_ptr()))
+    dims = [B, H, Hkv, D, M]        # ... and what the sizing function of the shape and window takes behind them
+    if shape:
+        extra += [count, 0]         # (token stride 0: packed rows)
+        dims.append(count)
+    if windowed:
+        extra.append(W)
+        dims.append(W)
+    fn = getattr(lib, "sfa_decode" + shape + flavour)
+    with torch.cuda.device(dev):
+        S = int(num_splits) if num_splits and num_splits > 0 else 0
+        if shape or windowed:
+            size = getattr(lib, "sfa_decode" + shape + ("_window" if windowed else "") + "_workspace_bytes")
+            ws = _workspace(dev, size(*dims, S))
+        else:
+            # the library sizes the split count by the KV heads (one workgroup serves a whole group); flash_decode and
+            # flash_decode_kv8 resolve an unset count themselves and pass it on
+            S = S or lib.sfa_decode_auto_splits(B, Hkv, D, M)
+            ws = _workspace(dev, lib.sfa_decode_workspace_bytes(B, H, D, M, S))
+            if sized_by_query_heads:
+                # (tests) the older contract of the C ABI: a caller that leaves the split count to the library sizes its
+                # workspace with sfa_decode_workspace_bytes(..., 0), which knows the query-head count only
+                S = 0
+                ws = torch.empty(lib.sfa_decode_workspace_bytes(B, H, D, M, 0), dtype=torch.uint8, device=dev)
+                _lib.check(lib.sfa_decode_reset_status(ctypes.c_void_p(ws.data_ptr()), _stream_ptr(dev)))
+        # (stride 0 of a chunk: n * (H + 2*Hkv) * D, computed by the library in 64 bit)
+        _call_decode(dev, a, 0 if shape else (H + 2 * Hkv) * D, S, ws, fn, extra)
+    return o
 
 
 def flash_decode(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o,
@@ -185,24 +269,10 @@ def flash_decode(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_
     [B, pages_per_seq]); memory_max_len is then the capacity of one sequence.
     num_heads_kv (grouped queries, an extension): qkv is then [B, num_heads + 2*num_heads_kv, D] (q heads,
     k heads, v heads), k_bias / v_bias and the caches carry num_heads_kv heads."""
-    lib = _lib.load()
-    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
-                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
-                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
-                                      kv_layout, block_table, num_heads_kv)
-    dev = qkv.device
-    with torch.cuda.device(dev):
-        # the library sizes the split count by the KV heads (one workgroup serves a whole group)
-        S = int(num_splits) if num_splits and num_splits > 0 else lib.sfa_decode_auto_splits(B, Hkv, D, M)
-        ws = _workspace(dev, lib.sfa_decode_workspace_bytes(B, H, D, M, S))
-        if _sized_by_query_heads:
-            # (tests) the older contract of the C ABI: a caller that leaves the split count to the library sizes its
-            # workspace with sfa_decode_workspace_bytes(..., 0), which knows the query-head count only
-            S = 0
-            ws = torch.empty(lib.sfa_decode_workspace_bytes(B, H, D, M, 0), dtype=torch.uint8, device=dev)
-            _lib.check(lib.sfa_decode_reset_status(ctypes.c_void_p(ws.data_ptr()), _stream_ptr(dev)))
-        _call_decode(dev, a, (H + 2 * Hkv) * D, S, ws, lib.sfa_decode)
-    return o
+    return _decode_op("", "", qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length, num_layer, idx_layer,
+                      num_splits, rotary_cos_table, rotary_sin_table, softmax_scale, kv_layout, block_table, num_heads_kv,
+                      sized_by_query_heads=_sized_by_query_heads)
 
 
 def flash_decode_window(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o,
@@ -214,26 +284,10 @@ def flash_decode_window(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_tabl
     pos = seq_len[b] attends to itself and the window - 1 cache rows before it, lo = max(0, pos + 1 - window) .. pos
     (flash-attn's window_size = (window - 1, 0)).  window >= 1; every other argument as in flash_decode.  Cache rows
     below lo, and block_table entries of pages wholly below lo, are never read.  Returns `o`."""
-    lib = _lib.load()
-    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
-                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
-                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
-                                      kv_layout, block_table, num_heads_kv)
-    W = int(window)
-    _require(-2 ** 31 <= W < 2 ** 31, f"window={window} does not fit an int")
-    dev = qkv.device
-    with torch.cuda.device(dev):
-        S = int(num_splits) if num_splits and num_splits > 0 else 0
-        ws = _workspace(dev, lib.sfa_decode_window_workspace_bytes(B, H, Hkv, D, M, W, S))
-        _call_decode(dev, a, (H + 2 * Hkv) * D, S, ws, lambda args, stream: lib.sfa_decode_window(args, W, stream))
-    return o
-
-
-def _kv8_scale(t, name, Hkv, dev):
-    if t is None:
-        return None
-    _check_gpu_tensor(t, name, torch.float32, (Hkv,), dev)
-    return ctypes.c_void_p(t.data_ptr())
+    return _decode_op("", "_window", qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length, num_layer, idx_layer,
+                      num_splits, rotary_cos_table, rotary_sin_table, softmax_scale, kv_layout, block_table, num_heads_kv,
+                      window=window)
 
 
 def flash_decode_kv8(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o,
@@ -245,18 +299,10 @@ def flash_decode_kv8(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, 
     torch.float8_e4m3fn tensors in flash_decode's layouts; qkv, the biases, the rotary tables and o stay fp16 / bf16;
     head_dim 64 or 128.  k_scale / v_scale: float32 device tensors [num_heads_kv], one scale per kv head, None = 1.0.
     The new token is stored as q8(x / scale) and attends through that stored value.  Returns `o`."""
-    lib = _lib.load()
-    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
-                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
-                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
-                                      kv_layout, block_table, num_heads_kv, kv8=True)
-    dev = qkv.device
-    ks, vs = _kv8_scale(k_scale, "k_scale", Hkv, dev), _kv8_scale(v_scale, "v_scale", Hkv, dev)
-    with torch.cuda.device(dev):
-        S = int(num_splits) if num_splits and num_splits > 0 else lib.sfa_decode_auto_splits(B, Hkv, D, M)
-        ws = _workspace(dev, lib.sfa_decode_workspace_bytes(B, H, D, M, S))
-        _call_decode(dev, a, (H + 2 * Hkv) * D, S, ws, lambda args, stream: lib.sfa_decode_kv8(args, ks, vs, stream))
-    return o
+    return _decode_op("", "_kv8", qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length, num_layer, idx_layer,
+                      num_splits, rotary_cos_table, rotary_sin_table, softmax_scale, kv_layout, block_table, num_heads_kv,
+                      k_scale=k_scale, v_scale=v_scale)
 
 
 def flash_decode_kv8_window(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o,
@@ -269,21 +315,10 @@ def flash_decode_kv8_window(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_
     window - 1 rows of the fp8 cache before it, lo = max(0, pos + 1 - window) .. pos.  window >= 1; the caches, the scales
     and every other argument as in flash_decode_kv8.  Cache rows below lo, and block_table entries of pages wholly below
     lo, are never read.  Returns `o`."""
-    lib = _lib.load()
-    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
-                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
-                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
-                                      kv_layout, block_table, num_heads_kv, kv8=True)
-    W = int(window)
-    _require(-2 ** 31 <= W < 2 ** 31, f"window={window} does not fit an int")
-    dev = qkv.device
-    ks, vs = _kv8_scale(k_scale, "k_scale", Hkv, dev), _kv8_scale(v_scale, "v_scale", Hkv, dev)
-    with torch.cuda.device(dev):
-        S = int(num_splits) if num_splits and num_splits > 0 else 0
-        ws = _workspace(dev, lib.sfa_decode_window_workspace_bytes(B, H, Hkv, D, M, W, S))
-        _call_decode(dev, a, (H + 2 * Hkv) * D, S, ws,
-                     lambda args, stream: lib.sfa_decode_kv8_window(args, ks, vs, W, stream))
-    return o
+    return _decode_op("", "_kv8_window", qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length, num_layer, idx_layer,
+                      num_splits, rotary_cos_table, rotary_sin_table, softmax_scale, kv_layout, block_table, num_heads_kv,
+                      window=window, k_scale=k_scale, v_scale=v_scale)
 
 
 def quantize_kv8(src, scale=None, out=None):
@@ -323,21 +358,9 @@ def flash_decode_chunk(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table
     appended to position seq_len[b] + t and attends to the cache rows [0, seq_len[b] + t].  seq_len is not
     incremented.  Ragged prompts: flash_decode_varlen, or pad to a common n (the rows past a sequence's real length are overwritten by the
     decode steps that follow, before anything reads them).  Returns `o`."""
-    lib = _lib.load()
-    _require(isinstance(qkv, torch.Tensor) and qkv.dim() in (4, 5),
-             f"qkv must be [B, n, 3, H, D] or [B, n, H + 2*Hkv, D] (got {tuple(getattr(qkv, 'shape', ()))})")
-    n = int(qkv.shape[1])
-    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
-                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
-                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
-                                      kv_layout, block_table, num_heads_kv, tokens=n)
-    dev = qkv.device
-    with torch.cuda.device(dev):
-        S = int(num_splits) if num_splits and num_splits > 0 else 0
-        ws = _workspace(dev, lib.sfa_decode_chunk_workspace_bytes(B, H, Hkv, D, M, n, S))
-        # (stride 0: n * (H + 2*Hkv) * D, computed by the library in 64 bit)
-        _call_decode(dev, a, 0, S, ws, lambda args, stream: lib.sfa_decode_chunk(args, n, 0, stream))
-    return o
+    return _decode_op("_chunk", "", qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length, num_layer, idx_layer,
+                      num_splits, rotary_cos_table, rotary_sin_table, softmax_scale, kv_layout, block_table, num_heads_kv)
 
 
 def flash_decode_varlen(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, cu_tokens,
@@ -352,22 +375,10 @@ def flash_decode_varlen(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_tabl
     rotated at and appended to position seq_len[b] + t and attends to the cache rows [0, seq_len[b] + t]; a sequence
     with no tokens takes no part, and no cache row past a sequence's own tokens is written.  cu_tokens is only read
     on the device (no synchronisation; graph replays may change it).  seq_len is not incremented.  Returns `o`."""
-    lib = _lib.load()
-    _require(isinstance(qkv, torch.Tensor) and qkv.dim() in (3, 4),
-             f"qkv must be [T, 3, H, D] or [T, H + 2*Hkv, D] (got {tuple(getattr(qkv, 'shape', ()))})")
-    T = int(qkv.shape[0])
-    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
-                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
-                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
-                                      kv_layout, block_table, num_heads_kv, packed=T)
-    dev = qkv.device
-    _check_gpu_tensor(cu_tokens, "cu_tokens", torch.int32, (B + 1,), dev)
-    with torch.cuda.device(dev):
-        S = int(num_splits) if num_splits and num_splits > 0 else 0
-        ws = _workspace(dev, lib.sfa_decode_varlen_workspace_bytes(B, H, Hkv, D, M, T, S))
-        cu = ctypes.c_void_p(cu_tokens.data_ptr())
-        _call_decode(dev, a, 0, S, ws, lambda args, stream: lib.sfa_decode_varlen(args, cu, T, 0, stream))
-    return o
+    return _decode_op("_varlen", "", qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length, num_layer, idx_layer,
+                      num_splits, rotary_cos_table, rotary_sin_table, softmax_scale, kv_layout, block_table, num_heads_kv,
+                      cu_tokens=cu_tokens)
 
 
 def flash_decode_chunk_kv8(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o,
@@ -380,21 +391,10 @@ def flash_decode_chunk_kv8(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_t
     float32 device tensors [num_heads_kv] or None = 1.0, as in flash_decode_kv8; every other argument as in
     flash_decode_chunk.  Token t is stored at row seq_len[b] + t as q8(x / scale) and attends to the rows
     [0, seq_len[b] + t] of the cache after the append, the new rows through their stored values.  Returns `o`."""
-    lib = _lib.load()
-    _require(isinstance(qkv, torch.Tensor) and qkv.dim() in (4, 5),
-             f"qkv must be [B, n, 3, H, D] or [B, n, H + 2*Hkv, D] (got {tuple(getattr(qkv, 'shape', ()))})")
-    n = int(qkv.shape[1])
-    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
-                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
-                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
-                                      kv_layout, block_table, num_heads_kv, tokens=n, kv8=True)
-    dev = qkv.device
-    ks, vs = _kv8_scale(k_scale, "k_scale", Hkv, dev), _kv8_scale(v_scale, "v_scale", Hkv, dev)
-    with torch.cuda.device(dev):
-        S = int(num_splits) if num_splits and num_splits > 0 else 0
-        ws = _workspace(dev, lib.sfa_decode_chunk_workspace_bytes(B, H, Hkv, D, M, n, S))
-        _call_decode(dev, a, 0, S, ws, lambda args, stream: lib.sfa_decode_chunk_kv8(args, ks, vs, n, 0, stream))
-    return o
+    return _decode_op("_chunk", "_kv8", qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length, num_layer, idx_layer,
+                      num_splits, rotary_cos_table, rotary_sin_table, softmax_scale, kv_layout, block_table, num_heads_kv,
+                      k_scale=k_scale, v_scale=v_scale)
 
 
 def flash_decode_varlen_kv8(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, cu_tokens,
@@ -405,29 +405,10 @@ def flash_decode_varlen_kv8(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_
     """flash_decode_varlen over an fp8 KV cache (include/star_flash_attn.h, sfa_decode_varlen_kv8): every packed token
     gets what flash_decode_chunk_kv8 gives it at pos = seq_len[b].  The caches and the scales as in flash_decode_kv8,
     every other argument as in flash_decode_varlen.  Returns `o`."""
-    lib = _lib.load()
-    _require(isinstance(qkv, torch.Tensor) and qkv.dim() in (3, 4),
-             f"qkv must be [T, 3, H, D] or [T, H + 2*Hkv, D] (got {tuple(getattr(qkv, 'shape', ()))})")
-    T = int(qkv.shape[0])
-    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
-                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
-                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
-                                      kv_layout, block_table, num_heads_kv, packed=T, kv8=True)
-    dev = qkv.device
-    ks, vs = _kv8_scale(k_scale, "k_scale", Hkv, dev), _kv8_scale(v_scale, "v_scale", Hkv, dev)
-    _check_gpu_tensor(cu_tokens, "cu_tokens", torch.int32, (B + 1,), dev)
-    with torch.cuda.device(dev):
-        S = int(num_splits) if num_splits and num_splits > 0 else 0
-        ws = _workspace(dev, lib.sfa_decode_varlen_workspace_bytes(B, H, Hkv, D, M, T, S))
-        cu = ctypes.c_void_p(cu_tokens.data_ptr())
-        _call_decode(dev, a, 0, S, ws, lambda args, stream: lib.sfa_decode_varlen_kv8(args, ks, vs, cu, T, 0, stream))
-    return o
-
-
-def _window_int(window):
-    W = int(window)
-    _require(-2 ** 31 <= W < 2 ** 31, f"window={window} does not fit an int")
-    return W
+    return _decode_op("_varlen", "_kv8", qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length, num_layer, idx_layer,
+                      num_splits, rotary_cos_table, rotary_sin_table, softmax_scale, kv_layout, block_table, num_heads_kv,
+                      cu_tokens=cu_tokens, k_scale=k_scale, v_scale=v_scale)
 
 
 def flash_decode_chunk_window(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o,
@@ -440,21 +421,10 @@ def flash_decode_chunk_window(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cach
     [max(0, seq_len[b] + t + 1 - window), seq_len[b] + t].  window >= 1; every other argument as in flash_decode_chunk.
     Cache rows below lo_0 = max(0, seq_len[b] + 1 - window), and block_table entries of pages wholly below lo_0, are
     never read.  Returns `o`."""
-    lib = _lib.load()
-    _require(isinstance(qkv, torch.Tensor) and qkv.dim() in (4, 5),
-             f"qkv must be [B, n, 3, H, D] or [B, n, H + 2*Hkv, D] (got {tuple(getattr(qkv, 'shape', ()))})")
-    n = int(qkv.shape[1])
-    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
-                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
-                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
-                                      kv_layout, block_table, num_heads_kv, tokens=n)
-    W = _window_int(window)
-    dev = qkv.device
-    with torch.cuda.device(dev):
-        S = int(num_splits) if num_splits and num_splits > 0 else 0
-        ws = _workspace(dev, lib.sfa_decode_chunk_window_workspace_bytes(B, H, Hkv, D, M, n, W, S))
-        _call_decode(dev, a, 0, S, ws, lambda args, stream: lib.sfa_decode_chunk_window(args, n, 0, W, stream))
-    return o
+    return _decode_op("_chunk", "_window", qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length, num_layer, idx_layer,
+                      num_splits, rotary_cos_table, rotary_sin_table, softmax_scale, kv_layout, block_table, num_heads_kv,
+                      window=window)
 
 
 def flash_decode_varlen_window(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, cu_tokens,
@@ -465,23 +435,10 @@ def flash_decode_varlen_window(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cac
     """flash_decode_varlen with a sliding window (include/star_flash_attn.h, sfa_decode_varlen_window): every packed
     token gets what flash_decode_chunk_window gives it at pos = seq_len[b].  window >= 1; every other argument as in
     flash_decode_varlen.  Returns `o`."""
-    lib = _lib.load()
-    _require(isinstance(qkv, torch.Tensor) and qkv.dim() in (3, 4),
-             f"qkv must be [T, 3, H, D] or [T, H + 2*Hkv, D] (got {tuple(getattr(qkv, 'shape', ()))})")
-    T = int(qkv.shape[0])
-    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
-                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
-                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
-                                      kv_layout, block_table, num_heads_kv, packed=T)
-    W = _window_int(window)
-    dev = qkv.device
-    _check_gpu_tensor(cu_tokens, "cu_tokens", torch.int32, (B + 1,), dev)
-    with torch.cuda.device(dev):
-        S = int(num_splits) if num_splits and num_splits > 0 else 0
-        ws = _workspace(dev, lib.sfa_decode_varlen_window_workspace_bytes(B, H, Hkv, D, M, T, W, S))
-        cu = ctypes.c_void_p(cu_tokens.data_ptr())
-        _call_decode(dev, a, 0, S, ws, lambda args, stream: lib.sfa_decode_varlen_window(args, cu, T, 0, W, stream))
-    return o
+    return _decode_op("_varlen", "_window", qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length, num_layer, idx_layer,
+                      num_splits, rotary_cos_table, rotary_sin_table, softmax_scale, kv_layout, block_table, num_heads_kv,
+                      cu_tokens=cu_tokens, window=window)
 
 
 def flash_decode_chunk_kv8_window(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o,
@@ -495,23 +452,10 @@ def flash_decode_chunk_kv8_window(qkv, q_bias, k_bias, v_bias, k_cache_table, v_
     their stored values.  window >= 1; the caches and the scales as in flash_decode_kv8, every other argument as in
     flash_decode_chunk.  Cache rows below lo_0 = max(0, seq_len[b] + 1 - window), and block_table entries of pages wholly
     below lo_0, are never read.  Returns `o`."""
-    lib = _lib.load()
-    _require(isinstance(qkv, torch.Tensor) and qkv.dim() in (4, 5),
-             f"qkv must be [B, n, 3, H, D] or [B, n, H + 2*Hkv, D] (got {tuple(getattr(qkv, 'shape', ()))})")
-    n = int(qkv.shape[1])
-    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
-                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
-                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
-                                      kv_layout, block_table, num_heads_kv, tokens=n, kv8=True)
-    W = _window_int(window)
-    dev = qkv.device
-    ks, vs = _kv8_scale(k_scale, "k_scale", Hkv, dev), _kv8_scale(v_scale, "v_scale", Hkv, dev)
-    with torch.cuda.device(dev):
-        S = int(num_splits) if num_splits and num_splits > 0 else 0
-        ws = _workspace(dev, lib.sfa_decode_chunk_window_workspace_bytes(B, H, Hkv, D, M, n, W, S))
-        _call_decode(dev, a, 0, S, ws,
-                     lambda args, stream: lib.sfa_decode_chunk_kv8_window(args, ks, vs, n, 0, W, stream))
-    return o
+    return _decode_op("_chunk", "_kv8_window", qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length, num_layer, idx_layer,
+                      num_splits, rotary_cos_table, rotary_sin_table, softmax_scale, kv_layout, block_table, num_heads_kv,
+                      window=window, k_scale=k_scale, v_scale=v_scale)
 
 
 def flash_decode_varlen_kv8_window(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, cu_tokens,
@@ -522,33 +466,10 @@ def flash_decode_varlen_kv8_window(qkv, q_bias, k_bias, v_bias, k_cache_table, v
     """flash_decode_varlen_kv8 with a sliding window (include/star_flash_attn.h, sfa_decode_varlen_kv8_window): every
     packed token gets what flash_decode_chunk_kv8_window gives it at pos = seq_len[b].  window >= 1; the caches and the
     scales as in flash_decode_kv8, every other argument as in flash_decode_varlen.  Returns `o`."""
-    lib = _lib.load()
-    _require(isinstance(qkv, torch.Tensor) and qkv.dim() in (3, 4),
-             f"qkv must be [T, 3, H, D] or [T, H + 2*Hkv, D] (got {tuple(getattr(qkv, 'shape', ()))})")
-    T = int(qkv.shape[0])
-    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
-                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
-                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
-                                      kv_layout, block_table, num_heads_kv, packed=T, kv8=True)
-    W = _window_int(window)
-    dev = qkv.device
-    ks, vs = _kv8_scale(k_scale, "k_scale", Hkv, dev), _kv8_scale(v_scale, "v_scale", Hkv, dev)
-    _check_gpu_tensor(cu_tokens, "cu_tokens", torch.int32, (B + 1,), dev)
-    with torch.cuda.device(dev):
-        S = int(num_splits) if num_splits and num_splits > 0 else 0
-        ws = _workspace(dev, lib.sfa_decode_varlen_window_workspace_bytes(B, H, Hkv, D, M, T, W, S))
-        cu = ctypes.c_void_p(cu_tokens.data_ptr())
-        _call_decode(dev, a, 0, S, ws,
-                     lambda args, stream: lib.sfa_decode_varlen_kv8_window(args, ks, vs, cu, T, 0, W, stream))
-    return o
-
-
-def _sinks_ptr(sinks, H, dev):
-    """sinks: None (NULL: the call is its _window twin) or a float32 [num_heads] device tensor, one logit per query head"""
-    if sinks is None:
-        return None
-    _check_gpu_tensor(sinks, "sinks", torch.float32, (H,), dev)
-    return ctypes.c_void_p(sinks.data_ptr())
+    return _decode_op("_varlen", "_kv8_window", qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length, num_layer, idx_layer,
+                      num_splits, rotary_cos_table, rotary_sin_table, softmax_scale, kv_layout, block_table, num_heads_kv,
+                      cu_tokens=cu_tokens, window=window, k_scale=k_scale, v_scale=v_scale)
 
 
 def flash_decode_window_sinks(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o,
@@ -560,20 +481,10 @@ def flash_decode_window_sinks(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cach
     device tensor [num_heads], is one more logit in query head h's softmax with a zero value row; it is not multiplied by
     the softmax scale.  sinks=None is flash_decode_window; window >= memory_max_len is full attention with sinks.  Every
     other argument as in flash_decode_window.  Returns `o`."""
-    lib = _lib.load()
-    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
-                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
-                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
-                                      kv_layout, block_table, num_heads_kv)
-    W = _window_int(window)
-    dev = qkv.device
-    sk = _sinks_ptr(sinks, H, dev)
-    with torch.cuda.device(dev):
-        S = int(num_splits) if num_splits and num_splits > 0 else 0
-        ws = _workspace(dev, lib.sfa_decode_window_workspace_bytes(B, H, Hkv, D, M, W, S))
-        _call_decode(dev, a, (H + 2 * Hkv) * D, S, ws,
-                     lambda args, stream: lib.sfa_decode_window_sinks(args, sk, W, stream))
-    return o
+    return _decode_op("", "_window_sinks", qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length, num_layer, idx_layer,
+                      num_splits, rotary_cos_table, rotary_sin_table, softmax_scale, kv_layout, block_table, num_heads_kv,
+                      window=window, sinks=sinks)
 
 
 def flash_decode_chunk_window_sinks(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o,
@@ -584,23 +495,10 @@ def flash_decode_chunk_window_sinks(qkv, q_bias, k_bias, v_bias, k_cache_table, 
     """flash_decode_chunk_window with attention sinks (include/star_flash_attn.h, sfa_decode_chunk_window_sinks): the
     result of n successive flash_decode_window_sinks calls.  sinks: float32 device tensor [num_heads] or None
     (= flash_decode_chunk_window); every other argument as in flash_decode_chunk_window.  Returns `o`."""
-    lib = _lib.load()
-    _require(isinstance(qkv, torch.Tensor) and qkv.dim() in (4, 5),
-             f"qkv must be [B, n, 3, H, D] or [B, n, H + 2*Hkv, D] (got {tuple(getattr(qkv, 'shape', ()))})")
-    n = int(qkv.shape[1])
-    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
-                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
-                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
-                                      kv_layout, block_table, num_heads_kv, tokens=n)
-    W = _window_int(window)
-    dev = qkv.device
-    sk = _sinks_ptr(sinks, H, dev)
-    with torch.cuda.device(dev):
-        S = int(num_splits) if num_splits and num_splits > 0 else 0
-        ws = _workspace(dev, lib.sfa_decode_chunk_window_workspace_bytes(B, H, Hkv, D, M, n, W, S))
-        _call_decode(dev, a, 0, S, ws,
-                     lambda args, stream: lib.sfa_decode_chunk_window_sinks(args, sk, n, 0, W, stream))
-    return o
+    return _decode_op("_chunk", "_window_sinks", qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length, num_layer, idx_layer,
+                      num_splits, rotary_cos_table, rotary_sin_table, softmax_scale, kv_layout, block_table, num_heads_kv,
+                      window=window, sinks=sinks)
 
 
 def flash_decode_varlen_window_sinks(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, cu_tokens,
@@ -612,25 +510,10 @@ def flash_decode_varlen_window_sinks(qkv, q_bias, k_bias, v_bias, k_cache_table,
     packed token gets what flash_decode_chunk_window_sinks gives it at pos = seq_len[b].  sinks: float32 device tensor
     [num_heads] or None (= flash_decode_varlen_window); every other argument as in flash_decode_varlen_window.
     Returns `o`."""
-    lib = _lib.load()
-    _require(isinstance(qkv, torch.Tensor) and qkv.dim() in (3, 4),
-             f"qkv must be [T, 3, H, D] or [T, H + 2*Hkv, D] (got {tuple(getattr(qkv, 'shape', ()))})")
-    T = int(qkv.shape[0])
-    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
-                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
-                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
-                                      kv_layout, block_table, num_heads_kv, packed=T)
-    W = _window_int(window)
-    dev = qkv.device
-    sk = _sinks_ptr(sinks, H, dev)
-    _check_gpu_tensor(cu_tokens, "cu_tokens", torch.int32, (B + 1,), dev)
-    with torch.cuda.device(dev):
-        S = int(num_splits) if num_splits and num_splits > 0 else 0
-        ws = _workspace(dev, lib.sfa_decode_varlen_window_workspace_bytes(B, H, Hkv, D, M, T, W, S))
-        cu = ctypes.c_void_p(cu_tokens.data_ptr())
-        _call_decode(dev, a, 0, S, ws,
-                     lambda args, stream: lib.sfa_decode_varlen_window_sinks(args, sk, cu, T, 0, W, stream))
-    return o
+    return _decode_op("_varlen", "_window_sinks", qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length, num_layer, idx_layer,
+                      num_splits, rotary_cos_table, rotary_sin_table, softmax_scale, kv_layout, block_table, num_heads_kv,
+                      cu_tokens=cu_tokens, window=window, sinks=sinks)
 
 
 def flash_decode_kv8_window_sinks(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o,
@@ -642,21 +525,10 @@ def flash_decode_kv8_window_sinks(qkv, q_bias, k_bias, v_bias, k_cache_table, v_
     float32 device tensor [num_heads], is one more logit in query head h's softmax with a zero value row; it is multiplied
     neither by the softmax scale nor by k_scale.  sinks=None is flash_decode_kv8_window; window >= memory_max_len is full
     attention with sinks.  Every other argument as in flash_decode_kv8_window.  Returns `o`."""
-    lib = _lib.load()
-    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
-                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
-                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
-                                      kv_layout, block_table, num_heads_kv, kv8=True)
-    W = _window_int(window)
-    dev = qkv.device
-    ks, vs = _kv8_scale(k_scale, "k_scale", Hkv, dev), _kv8_scale(v_scale, "v_scale", Hkv, dev)
-    sk = _sinks_ptr(sinks, H, dev)
-    with torch.cuda.device(dev):
-        S = int(num_splits) if num_splits and num_splits > 0 else 0
-        ws = _workspace(dev, lib.sfa_decode_window_workspace_bytes(B, H, Hkv, D, M, W, S))
-        _call_decode(dev, a, (H + 2 * Hkv) * D, S, ws,
-                     lambda args, stream: lib.sfa_decode_kv8_window_sinks(args, ks, vs, sk, W, stream))
-    return o
+    return _decode_op("", "_kv8_window_sinks", qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length, num_layer, idx_layer,
+                      num_splits, rotary_cos_table, rotary_sin_table, softmax_scale, kv_layout, block_table, num_heads_kv,
+                      window=window, sinks=sinks, k_scale=k_scale, v_scale=v_scale)
 
 
 def flash_decode_chunk_kv8_window_sinks(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o,
@@ -668,24 +540,10 @@ def flash_decode_chunk_kv8_window_sinks(qkv, q_bias, k_bias, v_bias, k_cache_tab
     """flash_decode_chunk_kv8_window with attention sinks (include/star_flash_attn.h, sfa_decode_chunk_kv8_window_sinks):
     the result of n successive flash_decode_kv8_window_sinks calls.  sinks: float32 device tensor [num_heads] or None
     (= flash_decode_chunk_kv8_window); every other argument as in flash_decode_chunk_kv8_window.  Returns `o`."""
-    lib = _lib.load()
-    _require(isinstance(qkv, torch.Tensor) and qkv.dim() in (4, 5),
-             f"qkv must be [B, n, 3, H, D] or [B, n, H + 2*Hkv, D] (got {tuple(getattr(qkv, 'shape', ()))})")
-    n = int(qkv.shape[1])
-    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
-                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
-                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
-                                      kv_layout, block_table, num_heads_kv, tokens=n, kv8=True)
-    W = _window_int(window)
-    dev = qkv.device
-    ks, vs = _kv8_scale(k_scale, "k_scale", Hkv, dev), _kv8_scale(v_scale, "v_scale", Hkv, dev)
-    sk = _sinks_ptr(sinks, H, dev)
-    with torch.cuda.device(dev):
-        S = int(num_splits) if num_splits and num_splits > 0 else 0
-        ws = _workspace(dev, lib.sfa_decode_chunk_window_workspace_bytes(B, H, Hkv, D, M, n, W, S))
-        _call_decode(dev, a, 0, S, ws,
-                     lambda args, stream: lib.sfa_decode_chunk_kv8_window_sinks(args, ks, vs, sk, n, 0, W, stream))
-    return o
+    return _decode_op("_chunk", "_kv8_window_sinks", qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length, num_layer, idx_layer,
+                      num_splits, rotary_cos_table, rotary_sin_table, softmax_scale, kv_layout, block_table, num_heads_kv,
+                      window=window, sinks=sinks, k_scale=k_scale, v_scale=v_scale)
 
 
 def flash_decode_varlen_kv8_window_sinks(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o,
@@ -698,26 +556,10 @@ def flash_decode_varlen_kv8_window_sinks(qkv, q_bias, k_bias, v_bias, k_cache_ta
     sfa_decode_varlen_kv8_window_sinks): every packed token gets what flash_decode_chunk_kv8_window_sinks gives it at
     pos = seq_len[b].  sinks: float32 device tensor [num_heads] or None (= flash_decode_varlen_kv8_window); every other
     argument as in flash_decode_varlen_kv8_window.  Returns `o`."""
-    lib = _lib.load()
-    _require(isinstance(qkv, torch.Tensor) and qkv.dim() in (3, 4),
-             f"qkv must be [T, 3, H, D] or [T, H + 2*Hkv, D] (got {tuple(getattr(qkv, 'shape', ()))})")
-    T = int(qkv.shape[0])
-    a, B, H, Hkv, D, M = _decode_args(qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
-                                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length,
-                                      num_layer, idx_layer, rotary_cos_table, rotary_sin_table, softmax_scale,
-                                      kv_layout, block_table, num_heads_kv, packed=T, kv8=True)
-    W = _window_int(window)
-    dev = qkv.device
-    ks, vs = _kv8_scale(k_scale, "k_scale", Hkv, dev), _kv8_scale(v_scale, "v_scale", Hkv, dev)
-    sk = _sinks_ptr(sinks, H, dev)
-    _check_gpu_tensor(cu_tokens, "cu_tokens", torch.int32, (B + 1,), dev)
-    with torch.cuda.device(dev):
-        S = int(num_splits) if num_splits and num_splits > 0 else 0
-        ws = _workspace(dev, lib.sfa_decode_varlen_window_workspace_bytes(B, H, Hkv, D, M, T, W, S))
-        cu = ctypes.c_void_p(cu_tokens.data_ptr())
-        _call_decode(dev, a, 0, S, ws,
-                     lambda args, stream: lib.sfa_decode_varlen_kv8_window_sinks(args, ks, vs, sk, cu, T, 0, W, stream))
-    return o
+    return _decode_op("_varlen", "_kv8_window_sinks", qkv, q_bias, k_bias, v_bias, k_cache_table, v_cache_table, seq_len, o, batch_size,
+                      memory_max_len, num_heads, head_dim, rotary_embedding_dim, max_input_length, num_layer, idx_layer,
+                      num_splits, rotary_cos_table, rotary_sin_table, softmax_scale, kv_layout, block_table, num_heads_kv,
+                      cu_tokens=cu_tokens, window=window, sinks=sinks, k_scale=k_scale, v_scale=v_scale)
 
 
 def check_decode_status(device=None):

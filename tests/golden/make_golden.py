@@ -149,7 +149,25 @@ def make_prefill():
     print("prefill_sdpa_cpu.npz", names)
 
 
+def make_decode_validation_matrix(lib_path):
+    """decode_validation_matrix.json: status and sfa_last_error() of every case of tests/decode_validation_cases.py, from
+    the libStarFlashAttention.so at lib_path -- one built at the commit whose host-side behaviour a change has to keep,
+    never the one under review.  Run where no GPU is (the cases pass fake device pointers)."""
+    import ctypes
+    import json
+    sys.path.insert(0, os.path.dirname(HERE))
+    import decode_validation_cases as dvc
+    assert not torch.cuda.is_available(), "record the validation matrix without a GPU"
+    got = dvc.run_all(ctypes.CDLL(os.path.abspath(lib_path)))
+    with open(os.path.join(HERE, "decode_validation_matrix.json"), "w") as f:     # one row (dvc.group) per line
+        f.write("[\n" + ",\n".join(json.dumps(row) for row in dvc.group(got)) + "\n]\n")
+    print("decode_validation_matrix.json", {k: len(v) for k, v in got.items()})
+
+
 if __name__ == "__main__":
+    if sys.argv[1:2] == ["decode_validation_matrix"]:    # python tests/golden/make_golden.py decode_validation_matrix LIB
+        make_decode_validation_matrix(sys.argv[2])
+        sys.exit(0)
     torch.set_num_threads(4)
     ref = load_reference()
     make_decode(ref)
