@@ -141,12 +141,13 @@ def _assemble(kind, dtype, D, G, Sq, Sk, slots, hot=None):
     return Problem(kind, dtype, D, G, Sq, Sk, q, k, v, spike, hot)
 
 
-def softmax_stress(kind, dtype, D, G, Sq, Sk):
-    """The problems of section A: one batch per kind and shape, a case per (batch, kv head)."""
+def softmax_stress(kind, dtype, D, G, Sq, Sk, spike_rows=SPIKE_ROWS):
+    """The problems of section A: one batch per kind and shape, a case per (batch, kv head).  spike_rows: the key rows of
+    the "spike" and "alone" cases (tests/prefill_window_cases.py adds rows next to the edges of its windows)."""
     slots = []
     if kind in ("spike", "alone"):
         # K[j*] = 4u among 0.25 N(0,1) keys; "alone": only the rows ALONE_ROWS are u (exactly), the others 0.25 N(0,1)
-        for j in [j for j in SPIKE_ROWS if j < Sk]:
+        for j in [j for j in spike_rows if j < Sk]:
             u, q, K, V = _frame(_rng(1, G, D, Sq, Sk, j), G, D, Sq, Sk)
             K[j] = 4.0 * u
             if kind == "alone":

@@ -28,7 +28,7 @@ for s in $STEPS; do
     decode) run_step decode 300 python -u -m pytest tests/test_decode_gpu.py -m gpu -x -q --timeout 120 ;;
     kv8chunk) run_step kv8chunk 300 python -u -m pytest tests/test_decode_chunk_kv8_gpu.py tests/test_decode_varlen_kv8_gpu.py -m gpu -q --timeout 120 --durations 5 ;;
     kv8chunkwin) run_step kv8chunkwin 300 python -u -m pytest tests/test_decode_chunk_kv8_window_gpu.py tests/test_decode_varlen_kv8_window_gpu.py -m gpu -q --timeout 120 --durations 5 ;;
-    numerics) run_step numerics 600 python -u -m pytest tests/test_decode_numerics_gpu.py tests/test_prefill_numerics_gpu.py -m gpu -q --timeout 120 --durations 5 ;;
+    numerics) run_step numerics 600 python -u -m pytest tests/test_decode_numerics_gpu.py tests/test_prefill_numerics_gpu.py tests/test_prefill_window_numerics_gpu.py -m gpu -q --timeout 120 --durations 5 ;;
     ab) run_step ab 300 python -u tools/prefill_ab.py ${AB_ARGS:-1 40} ;;
     w4) run_step w4 600 python -u -m pytest tests/test_prefill_gpu.py -m gpu -x -q --timeout 120 -k "w4 or flavours" ;;
     full) run_step full 900 python -u -m pytest tests/test_full_configs_gpu.py -m gpu -x -q --timeout 600 ;;
