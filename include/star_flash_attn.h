@@ -30,6 +30,7 @@
  *   sfa_decode_window_sinks     <- (no reference function: the three windowed calls with an attention sink per head)
  *   sfa_decode_kv8_window_sinks <- (no reference function: the three windowed fp8 calls with that sink)
  *   sfa_prefill_window_fwd      <- (no reference function: sfa_prefill_fwd with a sliding window and attention sinks)
+ *   sfa_prefill_split_fwd       <- (no reference function: sfa_prefill_fwd with each q-tile's key range split)
  * The Python-facing mha_fwd_cuda (src/flash_api.cpp:42-68) and the C++ template
  * surface (src/flash_attn.h) in this repo are thin layers over these symbols.
  */
@@ -68,7 +69,8 @@ extern "C" {
  *      sinks in the three windowed calls over an fp8 KV cache) added under the same version, in the same way; no sizing
  *      functions of their own either
  *      sfa_prefill_window_fwd (the prefill forward with a sliding window and attention sinks) added under the same
- *      version, beside an unchanged sfa_prefill_args: callers detect it by symbol */
+ *      version, beside an unchanged sfa_prefill_args: callers detect it by symbol; sfa_prefill_split_fwd (the prefill
+ *      forward with a split key range), its sizing function and its auto rule likewise */
 #define SFA_ABI_VERSION 4
 
 typedef enum sfa_status {
@@ -639,6 +641,56 @@ int sfa_prefill_fwd(const sfa_prefill_args *args, void *stream);
  */
 int sfa_prefill_window_fwd(const sfa_prefill_args *args, int window, const float *sinks, void *stream);
 
+/* ---- prefill with a split key range (small grids) ------------------------------------ */
+/*
+ * sfa_prefill_fwd for problems with fewer 256-row q-tiles than the chip has compute units -- a short query block against
+ * a long context (chunked prefill, prefix-cache hits), one sequence with few heads: the key range of every q-tile is cut
+ * into chunks, one workgroup walks each chunk, and a second kernel merges the fp32 partial results.  Added under ABI
+ * version 4, beside an unchanged sfa_prefill_args: callers detect the three functions by symbol.
+ * Semantics are exactly sfa_prefill_fwd's: the same o and lse, the same strides (elements, multiples of 8) and 16-byte
+ * alignment, GQA by heads_q % heads_kv == 0, fp16 / bf16, causal of either value (bottom-right aligned), softmax_scale
+ * <= 0 means 1/sqrt(head_dim), a row with no visible key gets zeros and lse = -inf (seqlen_k == 0: every row),
+ * batch == 0 or seqlen_q == 0 returns SFA_OK and launches nothing.  Only the work partition differs.  Except:
+ *   head_dim        64 or 128; 256 returns SFA_ERR_UNSUPPORTED_HEAD_DIM, as in sfa_prefill_window_fwd.
+ *   fast_scale      honoured only where the call forwards (below); the split kernels always use the exact scale.
+ *   num_splits      >= 1: explicit.  <= 0: sfa_prefill_auto_splits(batch, heads_q, seqlen_q, seqlen_k, head_dim, causal),
+ *                   and a workspace that holds fewer splits than that gets the largest count it holds (a NULL or empty
+ *                   one: 1), as in the decode calls.
+ *   workspace       device scratch of sfa_prefill_split_workspace_bytes(...) bytes, 256-byte aligned.  It has no status
+ *                   block and no contents that survive a call; it may hold anything on entry, NaN included.  Checked
+ *                   only when the resolved count (below) is above 1: NULL returns SFA_ERR_NULL_POINTER, a misaligned
+ *                   one SFA_ERR_BAD_SHAPE, too few bytes for an explicit num_splits SFA_ERR_WORKSPACE_TOO_SMALL.
+ * The checks of `args` come first, with the texts and the order of sfa_prefill_fwd's under this call's name.
+ * Partition.  nkt_max = ceil(seqlen_k / 64) is the number of 64-key tiles of the longest q-tile.  A request for S splits
+ * resolves to C = ceil(nkt_max / S) tiles per split and S' = ceil(nkt_max / C) <= S splits (5 tiles, S = 4: C = 2, S' = 3).
+ * Split s of q-tile qt (256 query rows) owns the tiles [s C, min((s + 1) C, nkt(qt))), where nkt(qt) is the number of
+ * tiles the q-tile's last row sees: nkt_max without a mask; under the causal mask lim / 64 + 1 with
+ * lim = min(256 (qt + 1), seqlen_q) - 1 + seqlen_k - seqlen_q, and 0 when lim < 0.  A split with s C >= nkt(qt) is empty:
+ * its workgroup reads no K or V and writes nothing.  Chunks have one length, so under the causal mask a short q-tile
+ * yields fewer partials, not thinner ones, and the partial traffic -- 4 (head_dim + 2) bytes per row and split, written
+ * and read once -- stays proportional to the work.
+ * Forwarding: a resolved count of 1 launches exactly what sfa_prefill_fwd launches for the same args (fast_scale
+ * honoured); the output is bit-identical to it, sfa_debug_get("last_prefill_kernel") reports that kernel, and the
+ * workspace may be NULL.  Every resolved count above 1 runs csrc/prefill_split_kernel.hip's two kernels, after which
+ * last_prefill_kernel keeps its previous value.  sfa_debug_get("last_prefill_splits") reports the resolved count.
+ * Like every entry point it is asynchronous on `stream`, allocates nothing, never synchronises and may be captured in a
+ * graph: two launches on the one stream, no parallel branches.
+ * Not served: head_dim 256; a window or sinks together with the split (short windows need no split; full attention with
+ * sinks is a follow-up); a combine fused into the last-arriving split; a paged or fp8 K/V.
+ */
+int sfa_prefill_split_fwd(const sfa_prefill_args *args, int num_splits, void *workspace, size_t workspace_bytes,
+                          void *stream);
+/* Bytes of workspace for `num_splits` (as given to the call: >= 1 explicit, <= 0 the library's choice): a multiple of
+ * 256, the same for a request and the count it resolves to, non-decreasing in num_splits, 0 where the count resolves to 1.
+ * It does not depend on `causal` (the mask only leaves some partials unused).  Bad dimensions: 0. */
+size_t sfa_prefill_split_workspace_bytes(int batch, int heads_q, int seqlen_q, int seqlen_k, int head_dim, int causal,
+                                         int num_splits);
+/* The split count the library picks from the shapes alone (>= 1, at most ceil(seqlen_k / 64)): 1 whenever
+ * batch * heads_q * ceil(seqlen_q / 256) reaches the 256 compute units or the key range is too short to give every
+ * split its minimum chunk; otherwise the smallest count that brings the workgroups to the compute-unit count, capped
+ * (csrc/c_api.hip has the rule and its measurements). */
+int sfa_prefill_auto_splits(int batch, int heads_q, int seqlen_q, int seqlen_k, int head_dim, int causal);
+
 /* ---- test / A-B hooks: NOT part of the drop-in surface ------------------------------ */
 /* The launch paths read no environment variable; the test-suite and tools/ select kernel
  * variants through this call.  knob: "prefill_impl" (-1 auto; the kernel ids of csrc/prefill_common.h, see
@@ -650,7 +702,8 @@ int sfa_debug_set(const char *knob, int value);
 /* Read back: the knobs above, and "last_prefill_kernel" = which kernel the last sfa_prefill_fwd of this process
  * launched (the dispatcher's choice included): 1 / 3 the 8-wave 256-row kernel (exact / prescaled), 20 + f the 128-row
  * geometry, 40 + f the 4-wave persistent kernel (f: 1 prescaled, 2 exact), 60 / 61 the head_dim 256 kernels, -1 none
- * yet.  Unknown knob: INT_MIN.  (bench.py names its roofline kernel from this.) */
+ * yet; "last_prefill_splits" = the resolved split count of this process's last sfa_prefill_split_fwd, 1 if it
+ * forwarded, -1 if there was none yet.  Unknown knob: INT_MIN.  (bench.py names its roofline kernel from this.) */
 int sfa_debug_get(const char *knob);
 
 /* ---- small helpers the reference's C++ harness uses ----------------------------- */

@@ -15,7 +15,7 @@
 //   * biases are honoured (the reference accepts and drops them); an empty tensor means "none";
 //   * the call is asynchronous on the current stream -- no device-wide sync, no per-call malloc;
 //   * num_splits is chosen by the library (the reference hard-codes 4);
-//   * additive entry points: mha_fwd (prefill forward), compute_rotary_table, check_errors,
+//   * additive entry points: mha_fwd (prefill forward), mha_fwd_split (the same with a split key range), compute_rotary_table, check_errors,
 //     release_workspaces.
 #include <ATen/hip/HIPContext.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>      // PyTorch-ROCm tensors say "cuda"
@@ -267,6 +267,25 @@ std::vector<at::Tensor> mha_fwd_window(const at::Tensor &q, const at::Tensor &k,
     return {c.out};
 }
 
+// Prefill forward with each q-tile's key range cut into num_splits chunks (<= 0: the library's choice) and a combine over
+// the fp32 partials: mha_fwd's result for grids with fewer q-tiles than compute units (include/star_flash_attn.h).  The
+// partials live in the module's per-(device, stream) workspace, behind its 256-byte status block.
+std::vector<at::Tensor> mha_fwd_split(const at::Tensor &q, const at::Tensor &k, const at::Tensor &v, bool causal,
+                                      int64_t num_splits, double softmax_scale, bool return_lse) {
+    PrefillCall c = prefill_call(q, k, v, c10::nullopt, softmax_scale, return_lse);
+    TORCH_CHECK(num_splits >= INT_MIN && num_splits <= INT_MAX, "star_flash_attn: num_splits out of range, got ", num_splits);
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(q.device());
+    c.a.causal = causal ? 1 : 0;
+    hipStream_t stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(q.device().index()).stream();
+    const size_t need = sfa_prefill_split_workspace_bytes(c.a.batch, c.a.heads_q, c.a.seqlen_q, c.a.seqlen_k, c.a.head_dim,
+                                                          c.a.causal, (int)num_splits);
+    void *ws = nullptr;
+    if (need) ws = (char *)workspace(q.device(), stream, 256 + need).data_ptr() + 256;
+    check_status(sfa_prefill_split_fwd(&c.a, (int)num_splits, ws, need, stream), "mha_fwd_split");
+    if (return_lse) return {c.out, c.lse};
+    return {c.out};
+}
+
 std::vector<at::Tensor> compute_rotary_table(int max_seq_len, int rot_dim, at::ScalarType dtype, at::Device device) {
     at::Tensor c = at::empty({max_seq_len, rot_dim / 2}, at::TensorOptions().dtype(dtype).device(device));
     at::Tensor s = at::empty_like(c);
@@ -297,6 +316,10 @@ PYBIND11_MODULE(star_flash_attn, m) {
     m.def("mha_fwd_window", &mha_fwd_window,
           "Attention forward (prefill) under a sliding window with optional attention sinks: returns [out] or [out, lse]",
           py::arg("q"), py::arg("k"), py::arg("v"), py::arg("window"), py::arg("sinks") = py::none(),
+          py::arg("softmax_scale") = 0.0, py::arg("return_lse") = false);
+    m.def("mha_fwd_split", &mha_fwd_split,
+          "Attention forward (prefill) with a split key range for small grids: returns [out] or [out, lse]",
+          py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal") = false, py::arg("num_splits") = 0,
           py::arg("softmax_scale") = 0.0, py::arg("return_lse") = false);
     m.def("compute_rotary_table", &compute_rotary_table, "cos/sin LUT [max_seq_len, rot_dim/2]",
           py::arg("max_seq_len"), py::arg("rot_dim"), py::arg("dtype"), py::arg("device"));

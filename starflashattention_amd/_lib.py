@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = [
     "sfa_decode_window_sinks", "sfa_decode_chunk_window_sinks", "sfa_decode_varlen_window_sinks",
     "sfa_decode_kv8_window_sinks", "sfa_decode_chunk_kv8_window_sinks", "sfa_decode_varlen_kv8_window_sinks",
     "sfa_prefill_window_fwd",
+    "sfa_prefill_split_fwd", "sfa_prefill_split_workspace_bytes", "sfa_prefill_auto_splits",
 ]
 
 
@@ -128,6 +129,13 @@ def load():
     lib.sfa_prefill_fwd.argtypes = [ctypes.POINTER(PrefillArgs), ctypes.c_void_p]
     lib.sfa_prefill_window_fwd.restype = ctypes.c_int
     lib.sfa_prefill_window_fwd.argtypes = [ctypes.POINTER(PrefillArgs), ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    lib.sfa_prefill_split_fwd.restype = ctypes.c_int
+    lib.sfa_prefill_split_fwd.argtypes = [ctypes.POINTER(PrefillArgs), ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
+                                          ctypes.c_void_p]
+    lib.sfa_prefill_split_workspace_bytes.restype = ctypes.c_size_t
+    lib.sfa_prefill_split_workspace_bytes.argtypes = [ctypes.c_int] * 7
+    lib.sfa_prefill_auto_splits.restype = ctypes.c_int
+    lib.sfa_prefill_auto_splits.argtypes = [ctypes.c_int] * 6
     lib.sfa_compute_rotary_table.restype = ctypes.c_int
     lib.sfa_compute_rotary_table.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                              ctypes.c_int, ctypes.c_int, ctypes.c_void_p]

@@ -434,6 +434,7 @@ int sfa_debug_get(const char *knob) {
     if (!strcmp(knob, "decode_gqa_mfma")) return g_knobs.decode_gqa_mfma.load(std::memory_order_relaxed);
     if (!strcmp(knob, "bm128_one_wg")) return g_knobs.bm128_one_wg.load(std::memory_order_relaxed);
     if (!strcmp(knob, "last_prefill_kernel")) return g_knobs.last_prefill_kernel.load(std::memory_order_relaxed);
+    if (!strcmp(knob, "last_prefill_splits")) return g_knobs.last_prefill_splits.load(std::memory_order_relaxed);
     return INT_MIN;
 }
 
@@ -731,7 +732,7 @@ int sfa_kv8_quantize(void *dst, const void *src, const float *scale, int64_t row
 
 namespace {
 
-// What sfa_prefill_fwd and sfa_prefill_window_fwd check and marshal alike, under the name of the call.  d256: head_dim
+// What sfa_prefill_fwd, sfa_prefill_window_fwd and sfa_prefill_split_fwd check and marshal alike, under the name of the call.  d256: head_dim
 // 256 is served.  Returns a status; *launch is false where there is nothing to do (batch or seqlen_q of 0).  p->nq_tiles
 // and p->bh_per_xcd are set for seqlen_k > 0.
 int prefill_call(const char *name, const sfa_prefill_args *a, bool d256, PrefillKernelParams *pp, bool *launch) {
@@ -789,9 +790,114 @@ int prefill_call(const char *name, const sfa_prefill_args *a, bool d256, Prefill
     return SFA_OK;
 }
 
+// ---- sfa_prefill_split_fwd: the partition, the workspace and the auto rule (include/star_flash_attn.h) ----
+constexpr int kSplitTile = 64, kSplitRows = 256;    // prefill_split_kernel.hip's key tile and q-tile
+
+int split_key_tiles(int seqlen_k) { return (seqlen_k + kSplitTile - 1) / kSplitTile; }
+// a request for S >= 1 splits of nkt >= 1 tiles: C = ceil(nkt / S) tiles per split, S' = ceil(nkt / C) splits
+int split_chunk(int nkt, int S) { return (nkt + S - 1) / S; }
+int split_resolve(int nkt, int S) {
+    if (nkt <= 0) return 1;
+    const int C = split_chunk(nkt, S < nkt ? S : nkt);
+    return (nkt + C - 1) / C;
+}
+// partial rows of `splits` resolved splits: every q-tile has 256 of them per split; each is head_dim + 2 floats
+size_t split_bytes(int batch, int heads_q, int seqlen_q, int head_dim, int splits) {
+    if (splits <= 1) return 0;
+    const size_t rows = (size_t)batch * heads_q * ((seqlen_q + kSplitRows - 1) / kSplitRows) * splits * kSplitRows;
+    return rows * (head_dim + 2) * sizeof(float);   // (a multiple of 256: rows is one of 256)
+}
+
+// The auto rule.  A split pays only while the grid leaves compute units idle: with batch * heads_q * q-tiles workgroups
+// for 256 units it takes the smallest count that fills them, as long as every split keeps kSplitMinTiles key tiles, and at
+// most kSplitMaxSplits.  Measured (tools/prefill_split_bench.py, profiles/prefill_split_sweep.txt, bf16, head_dim 128):
+//   * The rule's count is the best or within 2 % of the best explicit count on every line where it splits: 64 q-tiles
+//     against 32768 keys 4 splits (263 us; 2: 394, 8: 276; unsplit 624), against 8192 keys 4 (81; unsplit 159); 32
+//     q-tiles against 32768 keys 8 (147; 4: 214, 16: 166; unsplit 619); 128 q-tiles of S = 4096, 2 (causal 67 against 84,
+//     full 82 against 89).  From 256 q-tiles on every explicit count loses (S = 4096, 16 heads: +18 % causal, +29 % full
+//     at 2 splits; 32 heads +69 % / +30 %; 4 x 32 heads +69 %), as it does where the persistent kernel already balances
+//     a causal grid (4 heads of S = 16384: +39 %) and on short rows (4 x 16 heads of S = 1024, head_dim 64: +51 %):
+//     the rule returns 1 on all of them.
+//   * Minimum chunk (--probe: 8 workgroups, so every count fits the chip at once): chunks of 8 tiles are the best or
+//     within 3 % of it at 16, 32, 64 and 128 key tiles (split / unsplit 0.98, 0.62, 0.40, 0.25); 4 tiles tie at 16 and 32
+//     tiles and are 15 % slower at 64; 1 tile loses to the unsplit call (1.34).  So 8, the starting value, stays.
+//   * Cap: 16 is the largest count any line measured (40.6 us against 42.5 at 8 for 8 q-tiles against 8192 keys); no
+//     line has reached a larger one, so the cap is what has been measured, not the 32 it started from.
+constexpr int kSplitMinTiles = 8, kSplitMaxSplits = 16;
+int split_auto(int batch, int heads_q, int seqlen_q, int seqlen_k) {
+    if (batch <= 0 || heads_q <= 0 || seqlen_q <= 0 || seqlen_k <= 0) return 1;
+    const long long wgs = (long long)batch * heads_q * ((seqlen_q + kSplitRows - 1) / kSplitRows);
+    if (wgs >= 256) return 1;
+    const int nkt = split_key_tiles(seqlen_k);
+    long long S = (256 + wgs - 1) / wgs;
+    if (S > nkt / kSplitMinTiles) S = nkt / kSplitMinTiles;
+    if (S > kSplitMaxSplits) S = kSplitMaxSplits;
+    return S < 2 ? 1 : split_resolve(nkt, (int)S);
+}
+
 }  // namespace
 
 extern "C" {
+
+size_t sfa_prefill_split_workspace_bytes(int batch, int heads_q, int seqlen_q, int seqlen_k, int head_dim, int causal,
+                                         int num_splits) {
+    (void)causal;
+    if (batch <= 0 || heads_q <= 0 || seqlen_q <= 0 || seqlen_k <= 0 || (head_dim != 64 && head_dim != 128)) return 0;
+    const int S = num_splits >= 1 ? split_resolve(split_key_tiles(seqlen_k), num_splits)
+                                  : split_auto(batch, heads_q, seqlen_q, seqlen_k);
+    return split_bytes(batch, heads_q, seqlen_q, head_dim, S);
+}
+
+int sfa_prefill_auto_splits(int batch, int heads_q, int seqlen_q, int seqlen_k, int head_dim, int causal) {
+    (void)head_dim;
+    (void)causal;
+    return split_auto(batch, heads_q, seqlen_q, seqlen_k);
+}
+
+// sfa_prefill_fwd with each q-tile's key range cut into splits.  A resolved count of 1: the call is sfa_prefill_fwd's,
+// launch and all
+int sfa_prefill_split_fwd(const sfa_prefill_args *a, int num_splits, void *workspace, size_t workspace_bytes,
+                          void *stream) {
+    static const char *const name = "sfa_prefill_split_fwd";
+    PrefillSplitKernelParams sp;
+    bool launch;
+    if (const int rc = prefill_call(name, a, false, &sp.base, &launch)) return rc;
+    if (!launch) return SFA_OK;
+    // ---- the resolved count ----
+    const int nkt = split_key_tiles(a->seqlen_k);
+    int S;
+    if (num_splits >= 1) {
+        S = split_resolve(nkt, num_splits);
+    } else {
+        // the library's choice, or the largest count the workspace holds (none: 1), as in the decode calls
+        S = split_auto(a->batch, a->heads_q, a->seqlen_q, a->seqlen_k);
+        if (workspace || workspace_bytes == 0)
+            while (S > 1 && split_bytes(a->batch, a->heads_q, a->seqlen_q, a->head_dim, S) > workspace_bytes)
+                S = split_resolve(nkt, S - 1);
+    }
+    if (S > 1) {
+        if (!workspace) return fail(SFA_ERR_NULL_POINTER, "%s: workspace is NULL (%d splits)", name, S);
+        if ((uintptr_t)workspace & 255) return fail(SFA_ERR_BAD_SHAPE, "%s: workspace must be 256-byte aligned", name);
+        const size_t need = split_bytes(a->batch, a->heads_q, a->seqlen_q, a->head_dim, S);
+        if (workspace_bytes < need)
+            return fail(SFA_ERR_WORKSPACE_TOO_SMALL, "%s: workspace has %zu bytes, need %zu", name, workspace_bytes, need);
+        const long long combine_blocks = (long long)a->batch * a->heads_q * ((a->seqlen_q + 7) / 8);
+        if ((long long)8 * sp.base.bh_per_xcd * sp.base.nq_tiles * S > 0x7fffffffll || combine_blocks > 0x7fffffffll)
+            return fail(SFA_ERR_BAD_SHAPE, "%s: grid too large", name);
+    }
+    g_knobs.last_prefill_splits.store(S, std::memory_order_relaxed);
+    if (a->seqlen_k == 0)       // no keys: every row is empty -> zeros, lse = -inf
+        return launch_prefill_no_keys(sp.base, a->head_dim, (hipStream_t)stream);
+    if (S == 1) return launch_prefill(sp.base, a->dtype, a->head_dim, a->causal != 0, (hipStream_t)stream);
+    sp.base.fast_scale = 0;
+    sp.num_splits = S;
+    sp.tiles_per_split = split_chunk(nkt, num_splits >= 1 && num_splits < nkt ? num_splits : S);
+    const size_t rows = (size_t)a->batch * a->heads_q * sp.base.nq_tiles * S * kSplitRows;
+    sp.part_o = (float *)workspace;
+    sp.part_ml = (float2 *)((char *)workspace + rows * a->head_dim * sizeof(float));
+    if (const int rc = launch_prefill_split(sp, a->dtype, a->head_dim, a->causal != 0, (hipStream_t)stream)) return rc;
+    return launch_prefill_split_combine(sp, a->dtype, a->head_dim, a->causal != 0, (hipStream_t)stream);
+}
 
 int sfa_prefill_fwd(const sfa_prefill_args *a, void *stream) {
     PrefillKernelParams p;

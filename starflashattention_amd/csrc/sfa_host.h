@@ -192,6 +192,18 @@ struct PrefillWindowKernelParams {
     const float *sinks;     // [Hq] fp32, one logit per query head (natural-log units, not scaled), or nullptr
 };
 
+// sfa_prefill_split_fwd (prefill_split_kernel.hip): the prefill forward with each q-tile's key range cut into num_splits
+// chunks of tiles_per_split 64-key tiles, one workgroup per (q-tile, chunk), and a combine over the fp32 partials.  The
+// split rides behind the unchanged parameters, as the window does above.  Partials of row r (< 256) of q-tile qt of
+// (batch, head) bh, split s: index ((bh * nq_tiles + qt) * num_splits + s) * 256 + r of part_ml, times head_dim of part_o.
+struct PrefillSplitKernelParams {
+    PrefillKernelParams base;   // every field keeps its meaning; nq_tiles = q-tiles (256 rows) per (batch, head)
+    float *part_o;          // workspace: un-normalised fp32 partial outputs
+    float2 *part_ml;        // workspace: (reference max in log2 units, row sum) of each partial
+    int num_splits;         // resolved count, >= 2
+    int tiles_per_split;    // ceil(ceil(Sk / 64) / requested splits)
+};
+
 int launch_decode(const DecodeKernelParams &p, int dtype, int head_dim, hipStream_t stream);     // decode_dispatch.hip
 // non-temporal cache loads? (both caches of elem_bytes per element against the Infinity Cache, or the decode_nt knob)
 bool decode_nt(const DecodeKernelParams &p, int head_dim, int elem_bytes);                       // decode_dispatch.hip
@@ -236,6 +248,11 @@ int launch_prefill(const PrefillKernelParams &p, int dtype, int head_dim, bool c
 int launch_prefill_no_keys(const PrefillKernelParams &p, int head_dim, hipStream_t stream);
 // prefill_window_kernel.hip: called by sfa_prefill_window_fwd only (validated dtype, head_dim 64 / 128, Sk > 0)
 int launch_prefill_window(const PrefillWindowKernelParams &p, int dtype, int head_dim, hipStream_t stream);
+// prefill_split_kernel.hip: called by sfa_prefill_split_fwd only (validated dtype, head_dim 64 / 128, Sk > 0, two or more
+// splits): the attention kernel over the split key ranges, then the combine, on the same stream
+int launch_prefill_split(const PrefillSplitKernelParams &p, int dtype, int head_dim, bool causal, hipStream_t stream);
+int launch_prefill_split_combine(const PrefillSplitKernelParams &p, int dtype, int head_dim, bool causal,
+                                 hipStream_t stream);
 int launch_rotary_table(void *cos_t, void *sin_t, int max_seq_len, int rot_dim, int dtype, hipStream_t stream);
 int launch_fill16(void *arr, uint16_t bits, size_t n, hipStream_t stream);
 
@@ -250,6 +267,7 @@ struct DebugKnobs {
     std::atomic<int> decode_gqa_mfma{-1};   // decode_dispatch.hip: 0 forces the VALU grouped-query kernel
     std::atomic<int> bm128_one_wg{-1};      // prefill_kernel_bm128.hip: 1 = one workgroup per CU (A/B library only)
     std::atomic<int> last_prefill_kernel{-1};   // written by launch_prefill: what ran last (sfa_debug_get)
+    std::atomic<int> last_prefill_splits{-1};   // written by sfa_prefill_split_fwd: the resolved split count (1: forwarded)
 };
 extern DebugKnobs g_knobs;
 

@@ -41,6 +41,7 @@ _DTYPES = {torch.float16: _lib.DTYPE_FP16, torch.bfloat16: _lib.DTYPE_BF16}
 _KV8_DTYPES = (torch.uint8, torch.float8_e4m3fn)     # an e4m3 cache, as bytes or as torch's own type
 
 _workspaces = {}          # (device index, stream) -> torch.uint8 tensor
+_STATUS_BYTES = 256   # the status block at the front of that tensor (the decode calls' sticky error word)
 _sync_checks = False
 
 
@@ -636,6 +637,47 @@ def flash_attn_window_fwd(q, k, v, window, sinks=None, softmax_scale=None, out=N
     a.fast_scale = 0
     with torch.cuda.device(dev):
         _lib.check(lib.sfa_prefill_window_fwd(ctypes.byref(a), W, _sinks_ptr(sinks, q.shape[1], dev), _stream_ptr(dev)))
+    return (out, lse) if return_lse else out
+
+
+def prefill_auto_splits(batch, heads_q, seqlen_q, seqlen_k, head_dim, causal=False):
+    """sfa_prefill_auto_splits: the split count flash_attn_split_fwd(num_splits=0) picks for these shapes."""
+    return _lib.load().sfa_prefill_auto_splits(batch, heads_q, seqlen_q, seqlen_k, head_dim, 1 if causal else 0)
+
+
+def prefill_split_workspace_bytes(batch, heads_q, seqlen_q, seqlen_k, head_dim, causal=False, num_splits=0):
+    """sfa_prefill_split_workspace_bytes: bytes of workspace flash_attn_split_fwd needs for num_splits (0: auto)."""
+    return _lib.load().sfa_prefill_split_workspace_bytes(batch, heads_q, seqlen_q, seqlen_k, head_dim,
+                                                         1 if causal else 0, int(num_splits))
+
+
+def flash_attn_split_fwd(q, k, v, causal=False, num_splits=0, softmax_scale=None, out=None, return_lse=False,
+                         fast_scale=False, workspace=None):
+    """flash_attn_fwd with each q-tile's key range cut into num_splits chunks, one workgroup each, and a combine over
+    the fp32 partials (sfa_prefill_split_fwd): for grids with fewer 256-row q-tiles than compute units -- a short query
+    block against a long context.  Same o and lse as flash_attn_fwd; D in {64, 128}.  num_splits <= 0: the library's
+    choice (prefill_auto_splits); a count that resolves to 1 is flash_attn_fwd's launch, bit for bit (fast_scale is
+    honoured only there).  workspace: None takes the cached per-(device, stream) scratch; a uint8 tensor on q's device
+    (prefill_split_workspace_bytes, 256-byte aligned) is passed as it is."""
+    lib = _lib.load()
+    a, out, lse, dev = _prefill_args(q, k, v, out, return_lse, softmax_scale)
+    a.causal = 1 if causal else 0
+    a.fast_scale = 1 if fast_scale else 0
+    _require(isinstance(num_splits, int) and not isinstance(num_splits, bool), f"num_splits={num_splits!r} must be an int")
+    B, Hq, Sq, D = q.shape
+    if workspace is None:
+        need = lib.sfa_prefill_split_workspace_bytes(B, Hq, Sq, k.shape[2], D, a.causal, num_splits)
+        # behind the 256-byte status block of the decode calls, whose sticky word this call must not overwrite
+        ws = _workspace(dev, _STATUS_BYTES + need)[_STATUS_BYTES:] if need else None
+    else:
+        _require(isinstance(workspace, torch.Tensor) and workspace.dtype == torch.uint8 and workspace.dim() == 1 and
+                 workspace.is_contiguous(), "workspace must be a contiguous 1-d uint8 tensor")
+        _require(workspace.is_cuda and workspace.device == dev, f"workspace must be on {dev}")
+        ws = workspace
+    with torch.cuda.device(dev):
+        _lib.check(lib.sfa_prefill_split_fwd(ctypes.byref(a), num_splits,
+                                             ctypes.c_void_p(ws.data_ptr()) if ws is not None else None,
+                                             ws.numel() if ws is not None else 0, _stream_ptr(dev)))
     return (out, lse) if return_lse else out
 
 
