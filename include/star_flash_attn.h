@@ -31,6 +31,7 @@
  *   sfa_decode_kv8_window_sinks <- (no reference function: the three windowed fp8 calls with that sink)
  *   sfa_prefill_window_fwd      <- (no reference function: sfa_prefill_fwd with a sliding window and attention sinks)
  *   sfa_prefill_split_fwd       <- (no reference function: sfa_prefill_fwd with each q-tile's key range split)
+ *   sfa_prefill_varlen_fwd      <- (no reference function: sfa_prefill_fwd over packed sequences of different lengths)
  * The Python-facing mha_fwd_cuda (src/flash_api.cpp:42-68) and the C++ template
  * surface (src/flash_attn.h) in this repo are thin layers over these symbols.
  */
@@ -70,7 +71,9 @@ extern "C" {
  *      functions of their own either
  *      sfa_prefill_window_fwd (the prefill forward with a sliding window and attention sinks) added under the same
  *      version, beside an unchanged sfa_prefill_args: callers detect it by symbol; sfa_prefill_split_fwd (the prefill
- *      forward with a split key range), its sizing function and its auto rule likewise */
+ *      forward with a split key range), its sizing function and its auto rule likewise
+ *      sfa_prefill_varlen_fwd (the prefill forward over packed sequences of different lengths) and its sizing function
+ *      added under the same version with a struct of their own, sfa_prefill_varlen_args: callers detect them by symbol */
 #define SFA_ABI_VERSION 4
 
 typedef enum sfa_status {
@@ -690,6 +693,80 @@ size_t sfa_prefill_split_workspace_bytes(int batch, int heads_q, int seqlen_q, i
  * split its minimum chunk; otherwise the smallest count that brings the workgroups to the compute-unit count, capped
  * (csrc/c_api.hip has the rule and its measurements). */
 int sfa_prefill_auto_splits(int batch, int heads_q, int seqlen_q, int seqlen_k, int head_dim, int causal);
+
+/* ---- prefill over packed sequences of different lengths ------------------------------- */
+/*
+ * sfa_prefill_fwd for a batch whose sequences do not share one seqlen_q and one seqlen_k -- prompts of different lengths,
+ * chunked-prefill blocks against prefixes of different lengths -- in flash-attn's packed layout: the rows of all
+ * sequences one after another, delimited by cu_seqlens_q / cu_seqlens_k.  Added under ABI version 4 with a struct of its
+ * own, beside an unchanged sfa_prefill_args: callers detect the two functions by symbol.
+ *   q               [total_q, heads_q, head_dim]; k, v [total_k, heads_kv, head_dim]; o like q.  {token, head} strides in
+ *                   elements, >= 0 and multiples of 8, head_dim contiguous, 16-byte aligned.
+ *   lse             optional, fp32 [heads_q, total_q], contiguous, 4-byte aligned: the row of packed query row r of head h
+ *                   is h * total_q + r.
+ *   cu_seqlens_q, cu_seqlens_k   device int32 [batch + 1], 4-byte aligned.  Sequence b owns the packed query rows
+ *                   [cu_q[b], cu_q[b+1]) and the packed key rows [cu_k[b], cu_k[b+1]).  Read on the device only: the call
+ *                   never synchronises, and a captured graph may be replayed with other contents as long as batch,
+ *                   total_q and total_k stay the same.
+ *   total_q, total_k   host values: the rows the tensors hold, >= cu[batch].  They size the grid and the workspace.
+ *   head_dim        64 or 128; 256 returns SFA_ERR_UNSUPPORTED_HEAD_DIM: sfa_prefill_fwd is the call that serves it.
+ *   softmax_scale   <= 0 means 1/sqrt(head_dim).  There is no fast_scale: scores are always the fp32 Q.K^T times the scale
+ *                   in fp32.
+ *   workspace       device scratch of sfa_prefill_varlen_workspace_bytes(batch, total_q) bytes, 256-byte aligned.  It
+ *                   holds the plan only -- one 8-byte entry per work-item slot, total_q / 256 + batch of them -- and has
+ *                   no status block.  Its contents on entry never matter: every slot is written on every call.
+ * Semantics.  With n_q and n_k the row counts of sequence b, its o and lse rows are what sfa_prefill_fwd gives for
+ * batch = 1, seqlen_q = n_q, seqlen_k = n_k on those rows: exact scale, fp32 scores, GQA by heads_q % heads_kv == 0,
+ * fp16 / bf16, causal of either value, bottom-right aligned per sequence (key j visible to row i iff j <= i + (n_k - n_q)),
+ * a row with no visible key gets zeros and lse = -inf -- every row of a sequence with n_k == 0.  A sequence with
+ * n_q == 0 takes no part.
+ * A sequence is valid iff 0 <= cu[b] <= cu[b+1] <= total holds in both arrays; every kernel re-derives this for the
+ * sequence it serves.  An invalid sequence is skipped: none of its rows is read or written.  There is no status word:
+ * a caller that needs to know checks its cu arrays itself.
+ * What the call promises about memory: packed rows that belong to no valid sequence -- the rows between cu_q[batch] and
+ * total_q included -- are neither read nor written, in o and lse as in q, k and v.  The workgroups of sequence b read no
+ * K or V row outside [cu_k[b], cu_k[b+1]) and no q row outside [cu_q[b], cu_q[b+1]) (ragged last tiles clamp to the
+ * sequence's own last row), and write no o row outside it.  So a valid sequence's result is a function of its own rows
+ * only, bit-identical whether it is computed alone or inside any batch.
+ * Argument checks, in this order: args NULL; q / k / v / o / cu_seqlens_q / cu_seqlens_k NULL (SFA_ERR_NULL_POINTER);
+ * batch < 0, a head count <= 0, total_q < 0 or total_k < 0; heads_q % heads_kv != 0 (SFA_ERR_BAD_SHAPE); head_dim
+ * (SFA_ERR_UNSUPPORTED_HEAD_DIM); dtype (SFA_ERR_BAD_DTYPE); strides; alignment (SFA_ERR_BAD_SHAPE).  Then batch == 0 or
+ * total_q == 0 returns SFA_OK: nothing is launched and the workspace is not looked at.  Then the workspace: NULL
+ * (SFA_ERR_NULL_POINTER), not 256-byte aligned (SFA_ERR_BAD_SHAPE), too small (SFA_ERR_WORKSPACE_TOO_SMALL).  Last, a
+ * grid of (total_q / 256 + batch) * heads_q workgroups that does not fit 2^31 - 1 (SFA_ERR_BAD_SHAPE).
+ * Runs csrc/prefill_varlen_kernel.hip's two kernels; sfa_debug_get("last_prefill_kernel") and "last_prefill_splits" keep
+ * their values.  Like every entry point it is asynchronous on `stream`, allocates nothing, never synchronises and may be
+ * captured in a graph: two launches on the one stream, no parallel branches.
+ * Not served: head_dim 256; a sliding window or sinks; a key-range split for batches of few q-tiles; a paged or fp8 K/V;
+ * a status word for bad cu_seqlens; backward.
+ */
+typedef struct sfa_prefill_varlen_args {
+    const void *q;
+    const void *k;
+    const void *v;
+    void *o;
+    float *lse;                     /* may be NULL                                    */
+    const void *cu_seqlens_q;       /* device int32 [batch + 1]                       */
+    const void *cu_seqlens_k;       /* device int32 [batch + 1]                       */
+    int batch;
+    int heads_q;
+    int heads_kv;
+    int total_q;
+    int total_k;
+    int head_dim;                   /* 64 or 128                                      */
+    int64_t q_stride[2];            /* {token, head} strides in elements              */
+    int64_t k_stride[2];
+    int64_t v_stride[2];
+    int64_t o_stride[2];
+    float softmax_scale;            /* <= 0 => 1/sqrt(head_dim)                       */
+    int causal;
+    int dtype;                      /* sfa_dtype                                      */
+} sfa_prefill_varlen_args;
+
+int sfa_prefill_varlen_fwd(const sfa_prefill_varlen_args *args, void *workspace, size_t workspace_bytes, void *stream);
+/* Bytes of workspace: 8 * (total_q / 256 + batch) rounded up to a multiple of 256; non-decreasing in both arguments.
+ * batch <= 0 or total_q <= 0: 0. */
+size_t sfa_prefill_varlen_workspace_bytes(int batch, int total_q);
 
 /* ---- test / A-B hooks: NOT part of the drop-in surface ------------------------------ */
 /* The launch paths read no environment variable; the test-suite and tools/ select kernel

@@ -15,7 +15,7 @@
 //   * biases are honoured (the reference accepts and drops them); an empty tensor means "none";
 //   * the call is asynchronous on the current stream -- no device-wide sync, no per-call malloc;
 //   * num_splits is chosen by the library (the reference hard-codes 4);
-//   * additive entry points: mha_fwd (prefill forward), mha_fwd_split (the same with a split key range), compute_rotary_table, check_errors,
+//   * additive entry points: mha_fwd (prefill forward), mha_fwd_split (the same with a split key range), mha_varlen_fwd (the same over packed sequences), compute_rotary_table, check_errors,
 //     release_workspaces.
 #include <ATen/hip/HIPContext.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>      // PyTorch-ROCm tensors say "cuda"
@@ -286,6 +286,57 @@ std::vector<at::Tensor> mha_fwd_split(const at::Tensor &q, const at::Tensor &k, 
     return {c.out};
 }
 
+// Prefill forward over packed sequences of different lengths: q [Tq, Hq, D], k / v [Tk, Hkv, D] (head_dim contiguous,
+// any token and head strides), cu_seqlens_q / cu_seqlens_k int32 [B + 1] on q's device, read there only
+// (include/star_flash_attn.h).  Returns [out] or [out, lse [Hq, Tq]].  The plan lives in the module's per-(device,
+// stream) workspace, behind its 256-byte status block.
+std::vector<at::Tensor> mha_varlen_fwd(const at::Tensor &q, const at::Tensor &k, const at::Tensor &v,
+                                       const at::Tensor &cu_seqlens_q, const at::Tensor &cu_seqlens_k, bool causal,
+                                       double softmax_scale, bool return_lse) {
+    TORCH_CHECK(q.defined() && q.is_cuda(), "star_flash_attn: q must live on a HIP device");
+    const int dt = dtype_code(q, "q");
+    for (const at::Tensor *t : {&q, &k, &v}) {
+        TORCH_CHECK(t->is_cuda() && t->device() == q.device(), "star_flash_attn: q, k, v must share a device");
+        TORCH_CHECK(t->scalar_type() == q.scalar_type(), "star_flash_attn: q, k, v must share a dtype");
+        TORCH_CHECK(t->dim() == 3 && t->stride(2) == 1, "star_flash_attn: expected [tokens, heads, head_dim] with contiguous head_dim");
+    }
+    TORCH_CHECK(k.sizes() == v.sizes() && k.size(2) == q.size(2),
+                "star_flash_attn: k/v shapes ", k.sizes(), " / ", v.sizes(), " do not match q ", q.sizes());
+    for (const at::Tensor *t : {&cu_seqlens_q, &cu_seqlens_k})
+        TORCH_CHECK(t->is_cuda() && t->device() == q.device() && t->scalar_type() == at::kInt && t->dim() == 1 &&
+                    t->size(0) >= 1 && t->is_contiguous(),
+                    "star_flash_attn: cu_seqlens_q / cu_seqlens_k must be contiguous int32 [batch + 1] tensors on q's device");
+    TORCH_CHECK(cu_seqlens_q.size(0) == cu_seqlens_k.size(0), "star_flash_attn: cu_seqlens_q has ", cu_seqlens_q.size(0),
+                " entries, cu_seqlens_k ", cu_seqlens_k.size(0));
+    TORCH_CHECK(q.size(0) <= INT_MAX && k.size(0) <= INT_MAX && cu_seqlens_q.size(0) <= INT_MAX,
+                "star_flash_attn: too many rows");
+    at::Tensor out = at::empty_like(q, q.options(), at::MemoryFormat::Contiguous);
+    at::Tensor lse;
+    if (return_lse) lse = at::empty({q.size(1), q.size(0)}, q.options().dtype(at::kFloat));
+
+    sfa_prefill_varlen_args a = {};
+    a.q = q.data_ptr(); a.k = k.data_ptr(); a.v = v.data_ptr(); a.o = out.data_ptr();
+    a.lse = return_lse ? lse.data_ptr<float>() : nullptr;
+    a.cu_seqlens_q = cu_seqlens_q.data_ptr(); a.cu_seqlens_k = cu_seqlens_k.data_ptr();
+    a.batch = (int)cu_seqlens_q.size(0) - 1; a.heads_q = (int)q.size(1); a.heads_kv = (int)k.size(1);
+    a.total_q = (int)q.size(0); a.total_k = (int)k.size(0); a.head_dim = (int)q.size(2);
+    for (int i = 0; i < 2; ++i) {
+        a.q_stride[i] = q.stride(i); a.k_stride[i] = k.stride(i);
+        a.v_stride[i] = v.stride(i); a.o_stride[i] = out.stride(i);
+    }
+    a.softmax_scale = (float)softmax_scale;
+    a.causal = causal ? 1 : 0;
+    a.dtype = dt;
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(q.device());
+    hipStream_t stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(q.device().index()).stream();
+    const size_t need = sfa_prefill_varlen_workspace_bytes(a.batch, a.total_q);
+    void *ws = nullptr;
+    if (need) ws = (char *)workspace(q.device(), stream, 256 + need).data_ptr() + 256;
+    check_status(sfa_prefill_varlen_fwd(&a, ws, need, stream), "mha_varlen_fwd");
+    if (return_lse) return {out, lse};
+    return {out};
+}
+
 std::vector<at::Tensor> compute_rotary_table(int max_seq_len, int rot_dim, at::ScalarType dtype, at::Device device) {
     at::Tensor c = at::empty({max_seq_len, rot_dim / 2}, at::TensorOptions().dtype(dtype).device(device));
     at::Tensor s = at::empty_like(c);
@@ -321,6 +372,10 @@ PYBIND11_MODULE(star_flash_attn, m) {
           "Attention forward (prefill) with a split key range for small grids: returns [out] or [out, lse]",
           py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal") = false, py::arg("num_splits") = 0,
           py::arg("softmax_scale") = 0.0, py::arg("return_lse") = false);
+    m.def("mha_varlen_fwd", &mha_varlen_fwd,
+          "Attention forward (prefill) over packed sequences of different lengths: returns [out] or [out, lse]",
+          py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cu_seqlens_q"), py::arg("cu_seqlens_k"),
+          py::arg("causal") = false, py::arg("softmax_scale") = 0.0, py::arg("return_lse") = false);
     m.def("compute_rotary_table", &compute_rotary_table, "cos/sin LUT [max_seq_len, rot_dim/2]",
           py::arg("max_seq_len"), py::arg("rot_dim"), py::arg("dtype"), py::arg("device"));
 }

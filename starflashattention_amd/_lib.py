@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = [
     "sfa_decode_kv8_window_sinks", "sfa_decode_chunk_kv8_window_sinks", "sfa_decode_varlen_kv8_window_sinks",
     "sfa_prefill_window_fwd",
     "sfa_prefill_split_fwd", "sfa_prefill_split_workspace_bytes", "sfa_prefill_auto_splits",
+    "sfa_prefill_varlen_fwd", "sfa_prefill_varlen_workspace_bytes",
 ]
 
 
@@ -70,6 +71,19 @@ class PrefillArgs(ctypes.Structure):
         ("v_stride", ctypes.c_int64 * 3), ("o_stride", ctypes.c_int64 * 3),
         ("softmax_scale", ctypes.c_float), ("causal", ctypes.c_int), ("dtype", ctypes.c_int),
         ("fast_scale", ctypes.c_int),
+    ]
+
+
+class PrefillVarlenArgs(ctypes.Structure):
+    """struct sfa_prefill_varlen_args"""
+    _fields_ = [
+        ("q", ctypes.c_void_p), ("k", ctypes.c_void_p), ("v", ctypes.c_void_p), ("o", ctypes.c_void_p),
+        ("lse", ctypes.c_void_p), ("cu_seqlens_q", ctypes.c_void_p), ("cu_seqlens_k", ctypes.c_void_p),
+        ("batch", ctypes.c_int), ("heads_q", ctypes.c_int), ("heads_kv", ctypes.c_int),
+        ("total_q", ctypes.c_int), ("total_k", ctypes.c_int), ("head_dim", ctypes.c_int),
+        ("q_stride", ctypes.c_int64 * 2), ("k_stride", ctypes.c_int64 * 2),
+        ("v_stride", ctypes.c_int64 * 2), ("o_stride", ctypes.c_int64 * 2),
+        ("softmax_scale", ctypes.c_float), ("causal", ctypes.c_int), ("dtype", ctypes.c_int),
     ]
 
 
@@ -136,6 +150,11 @@ def load():
     lib.sfa_prefill_split_workspace_bytes.argtypes = [ctypes.c_int] * 7
     lib.sfa_prefill_auto_splits.restype = ctypes.c_int
     lib.sfa_prefill_auto_splits.argtypes = [ctypes.c_int] * 6
+    lib.sfa_prefill_varlen_fwd.restype = ctypes.c_int
+    lib.sfa_prefill_varlen_fwd.argtypes = [ctypes.POINTER(PrefillVarlenArgs), ctypes.c_void_p, ctypes.c_size_t,
+                                           ctypes.c_void_p]
+    lib.sfa_prefill_varlen_workspace_bytes.restype = ctypes.c_size_t
+    lib.sfa_prefill_varlen_workspace_bytes.argtypes = [ctypes.c_int] * 2
     lib.sfa_compute_rotary_table.restype = ctypes.c_int
     lib.sfa_compute_rotary_table.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                              ctypes.c_int, ctypes.c_int, ctypes.c_void_p]

@@ -204,6 +204,23 @@ struct PrefillSplitKernelParams {
     int tiles_per_split;    // ceil(ceil(Sk / 64) / requested splits)
 };
 
+// sfa_prefill_varlen_fwd (prefill_varlen_kernel.hip): the prefill forward over packed sequences of different lengths.
+// Sequence b owns the q / o rows [cu_q[b], cu_q[b+1]) and the k / v rows [cu_k[b], cu_k[b+1]); the cu arrays are read on
+// the device only.  The workspace is the plan alone: int2 (b, q_tile) per workgroup slot, b = -1 = empty.
+struct PrefillVarlenKernelParams {
+    const uint16_t *q, *k, *v;
+    uint16_t *o;
+    float *lse;             // [Hq, total_q] or nullptr
+    const int32_t *cu_q, *cu_k;     // [B + 1] each
+    int2 *plan;             // workspace: [bound]
+    int B, Hq, Hkv;
+    int total_q, total_k;   // host bounds of cu_q[B] / cu_k[B]: rows of q, o / k, v
+    int bound;              // plan entries = total_q / 256 + B; the attention grid is bound * Hq workgroups
+    int slices;             // 8 (Hq % 8 == 0: blockIdx & 7 selects Hq / 8 query heads) or 1
+    long long qs[2], ks[2], vs[2], os[2];   // {token, head} strides (elements)
+    float scale_log2;
+};
+
 int launch_decode(const DecodeKernelParams &p, int dtype, int head_dim, hipStream_t stream);     // decode_dispatch.hip
 // non-temporal cache loads? (both caches of elem_bytes per element against the Infinity Cache, or the decode_nt knob)
 bool decode_nt(const DecodeKernelParams &p, int head_dim, int elem_bytes);                       // decode_dispatch.hip
@@ -253,6 +270,9 @@ int launch_prefill_window(const PrefillWindowKernelParams &p, int dtype, int hea
 int launch_prefill_split(const PrefillSplitKernelParams &p, int dtype, int head_dim, bool causal, hipStream_t stream);
 int launch_prefill_split_combine(const PrefillSplitKernelParams &p, int dtype, int head_dim, bool causal,
                                  hipStream_t stream);
+// prefill_varlen_kernel.hip: called by sfa_prefill_varlen_fwd only (validated dtype, head_dim 64 / 128, B > 0, total_q >
+// 0): the plan kernel, then the attention kernel over the plan, on the same stream
+int launch_prefill_varlen(const PrefillVarlenKernelParams &p, int dtype, int head_dim, bool causal, hipStream_t stream);
 int launch_rotary_table(void *cos_t, void *sin_t, int max_seq_len, int rot_dim, int dtype, hipStream_t stream);
 int launch_fill16(void *arr, uint16_t bits, size_t n, hipStream_t stream);
 

@@ -28,6 +28,9 @@ libStarFlashAttention.so.  The public operators:
   flash_decode_kv8_window_sinks(...) / flash_decode_chunk_kv8_window_sinks(...) /
   flash_decode_varlen_kv8_window_sinks(...)  the same sink in the three windowed calls over an fp8 KV cache (new entry
                       points).
+  flash_attn_window_fwd(...) / flash_attn_split_fwd(...) / flash_attn_varlen_fwd(...)  flash_attn_fwd under a sliding
+                      window with attention sinks, with a split key range for small grids, and over packed sequences of
+                      different lengths delimited by cu_seqlens_q / cu_seqlens_k (new entry points).
 """
 import ctypes
 import math
@@ -678,6 +681,77 @@ def flash_attn_split_fwd(q, k, v, causal=False, num_splits=0, softmax_scale=None
         _lib.check(lib.sfa_prefill_split_fwd(ctypes.byref(a), num_splits,
                                              ctypes.c_void_p(ws.data_ptr()) if ws is not None else None,
                                              ws.numel() if ws is not None else 0, _stream_ptr(dev)))
+    return (out, lse) if return_lse else out
+
+
+def prefill_varlen_workspace_bytes(batch, total_q):
+    """sfa_prefill_varlen_workspace_bytes: bytes of workspace flash_attn_varlen_fwd needs (the plan: 8 bytes per slot,
+    total_q // 256 + batch slots, rounded up to 256)."""
+    return _lib.load().sfa_prefill_varlen_workspace_bytes(int(batch), int(total_q))
+
+
+def flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, causal=False, softmax_scale=None, out=None,
+                          return_lse=False, workspace=None):
+    """flash_attn_fwd over packed sequences of different lengths (sfa_prefill_varlen_fwd).  q [Tq, Hq, D], k / v
+    [Tk, Hkv, D] with any token and head strides and D contiguous, fp16 or bf16, D in {64, 128}; cu_seqlens_q /
+    cu_seqlens_k int32 [B + 1] tensors on q's device: sequence b owns the query rows [cu_q[b], cu_q[b+1]) and the key rows
+    [cu_k[b], cu_k[b+1]) and gets what flash_attn_fwd gives for those rows alone (causal: bottom-right aligned per
+    sequence).  The cu tensors are read on the device only (no synchronisation; a graph replay may change them); a
+    sequence whose entries are not a range of the tensors is skipped, and rows of no sequence keep their contents.
+    workspace: None takes the cached per-(device, stream) scratch; a uint8 tensor on q's device
+    (prefill_varlen_workspace_bytes, 256-byte aligned) is passed as it is.  Returns out [Tq, Hq, D], with return_lse
+    (out, lse [Hq, Tq])."""
+    _require(isinstance(q, torch.Tensor) and q.dtype in _DTYPES,
+             f"q must be float16 or bfloat16 (got {getattr(q, 'dtype', type(q))})")
+    dt, dev = q.dtype, q.device
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        _require(isinstance(t, torch.Tensor) and t.device == dev, f"{name} must be a tensor on {dev}")
+        _require(t.dtype == dt, f"{name} dtype {t.dtype} != {dt}")
+        _require(t.dim() == 3, f"{name} must be [tokens, heads, head_dim]")
+        _require(t.stride(2) == 1, f"{name}: head_dim must be contiguous")
+    Tq, Hq, D = (int(x) for x in q.shape)
+    _require(k.shape == v.shape and k.shape[2] == D,
+             f"k/v shapes {tuple(k.shape)}/{tuple(v.shape)} do not match q {tuple(q.shape)}")
+    Tk, Hkv = int(k.shape[0]), int(k.shape[1])
+    for name, t in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
+        _require(isinstance(t, torch.Tensor), f"{name} must be a tensor")
+        _require(t.dtype == torch.int32, f"{name} has dtype {t.dtype}, expected torch.int32")
+        _require(t.device == dev, f"{name} is on {t.device}, expected {dev}")
+        _require(t.dim() == 1 and t.numel() >= 1 and t.is_contiguous(), f"{name} must be a contiguous [batch + 1] tensor")
+    _require(cu_seqlens_q.numel() == cu_seqlens_k.numel(),
+             f"cu_seqlens_q has {cu_seqlens_q.numel()} entries, cu_seqlens_k {cu_seqlens_k.numel()}")
+    B = cu_seqlens_q.numel() - 1
+    if out is None:
+        out = torch.empty((Tq, Hq, D), dtype=dt, device=dev)
+    else:
+        _require(isinstance(out, torch.Tensor) and out.shape == q.shape and out.dtype == dt and out.device == dev and
+                 out.stride(2) == 1, "out must match q in shape/dtype/device with contiguous head_dim")
+    if workspace is not None:
+        _require(isinstance(workspace, torch.Tensor) and workspace.dtype == torch.uint8 and workspace.dim() == 1 and
+                 workspace.is_contiguous(), "workspace must be a contiguous 1-d uint8 tensor")
+        _require(workspace.device == dev, f"workspace must be on {dev}")
+    _require(q.is_cuda, f"q must live on a HIP device (got {dev})")
+    lib = _lib.load()
+    lse = torch.empty((Hq, Tq), dtype=torch.float32, device=dev) if return_lse else None
+    a = _lib.PrefillVarlenArgs()
+    a.q, a.k, a.v, a.o = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
+    a.lse = lse.data_ptr() if lse is not None else None
+    a.cu_seqlens_q, a.cu_seqlens_k = cu_seqlens_q.data_ptr(), cu_seqlens_k.data_ptr()
+    a.batch, a.heads_q, a.heads_kv, a.total_q, a.total_k, a.head_dim = B, Hq, Hkv, Tq, Tk, D
+    for dst, t in ((a.q_stride, q), (a.k_stride, k), (a.v_stride, v), (a.o_stride, out)):
+        dst[0], dst[1] = t.stride(0), t.stride(1)
+    a.softmax_scale = float(softmax_scale) if softmax_scale else 0.0
+    a.causal = 1 if causal else 0
+    a.dtype = _DTYPES[dt]
+    if workspace is None:
+        need = lib.sfa_prefill_varlen_workspace_bytes(B, Tq)
+        # behind the 256-byte status block of the decode calls, whose sticky word this call must not overwrite
+        ws = _workspace(dev, _STATUS_BYTES + need)[_STATUS_BYTES:] if need else None
+    else:
+        ws = workspace
+    with torch.cuda.device(dev):
+        _lib.check(lib.sfa_prefill_varlen_fwd(ctypes.byref(a), ctypes.c_void_p(ws.data_ptr()) if ws is not None else None,
+                                              ws.numel() if ws is not None else 0, _stream_ptr(dev)))
     return (out, lse) if return_lse else out
 
 
