@@ -32,6 +32,7 @@
  *   sfa_prefill_window_fwd      <- (no reference function: sfa_prefill_fwd with a sliding window and attention sinks)
  *   sfa_prefill_split_fwd       <- (no reference function: sfa_prefill_fwd with each q-tile's key range split)
  *   sfa_prefill_varlen_fwd      <- (no reference function: sfa_prefill_fwd over packed sequences of different lengths)
+ *   sfa_prefill_varlen_window_fwd <- (no reference function: sfa_prefill_varlen_fwd with a sliding window and sinks)
  * The Python-facing mha_fwd_cuda (src/flash_api.cpp:42-68) and the C++ template
  * surface (src/flash_attn.h) in this repo are thin layers over these symbols.
  */
@@ -73,7 +74,9 @@ extern "C" {
  *      version, beside an unchanged sfa_prefill_args: callers detect it by symbol; sfa_prefill_split_fwd (the prefill
  *      forward with a split key range), its sizing function and its auto rule likewise
  *      sfa_prefill_varlen_fwd (the prefill forward over packed sequences of different lengths) and its sizing function
- *      added under the same version with a struct of their own, sfa_prefill_varlen_args: callers detect them by symbol */
+ *      added under the same version with a struct of their own, sfa_prefill_varlen_args: callers detect them by symbol
+ *      sfa_prefill_varlen_window_fwd (the packed prefill forward with a sliding window and attention sinks) added under
+ *      the same version beside an unchanged sfa_prefill_varlen_args: callers detect it by symbol */
 #define SFA_ABI_VERSION 4
 
 typedef enum sfa_status {
@@ -640,7 +643,8 @@ int sfa_prefill_fwd(const sfa_prefill_args *args, void *stream);
  * runs the windowed kernel (csrc/prefill_window_kernel.hip), after which last_prefill_kernel keeps its previous value.
  * Like every entry point it is asynchronous on `stream`, allocates nothing, never synchronises and may be captured in a
  * graph.
- * Not served: head_dim 256, two-sided windows, soft-capping, a paged or fp8 K/V, split key ranges.
+ * Not served: head_dim 256, two-sided windows, soft-capping, a paged or fp8 K/V, split key ranges.  (Packed sequences of
+ * different lengths: sfa_prefill_varlen_window_fwd, below.)
  */
 int sfa_prefill_window_fwd(const sfa_prefill_args *args, int window, const float *sinks, void *stream);
 
@@ -737,8 +741,8 @@ int sfa_prefill_auto_splits(int batch, int heads_q, int seqlen_q, int seqlen_k, 
  * Runs csrc/prefill_varlen_kernel.hip's two kernels; sfa_debug_get("last_prefill_kernel") and "last_prefill_splits" keep
  * their values.  Like every entry point it is asynchronous on `stream`, allocates nothing, never synchronises and may be
  * captured in a graph: two launches on the one stream, no parallel branches.
- * Not served: head_dim 256; a sliding window or sinks; a key-range split for batches of few q-tiles; a paged or fp8 K/V;
- * a status word for bad cu_seqlens; backward.
+ * Not served: head_dim 256; a key-range split for batches of few q-tiles; a paged or fp8 K/V; a status word for bad
+ * cu_seqlens; backward.  (A sliding window and sinks: sfa_prefill_varlen_window_fwd, below.)
  */
 typedef struct sfa_prefill_varlen_args {
     const void *q;
@@ -767,6 +771,47 @@ int sfa_prefill_varlen_fwd(const sfa_prefill_varlen_args *args, void *workspace,
 /* Bytes of workspace: 8 * (total_q / 256 + batch) rounded up to a multiple of 256; non-decreasing in both arguments.
  * batch <= 0 or total_q <= 0: 0. */
 size_t sfa_prefill_varlen_workspace_bytes(int batch, int total_q);
+
+/* ---- packed prefill with a sliding window and attention sinks -------------------------- */
+/*
+ * sfa_prefill_varlen_fwd for a layer whose causal mask is a sliding window and whose softmax may carry a learned per-head
+ * sink logit: sfa_prefill_window_fwd's mask and sink on sfa_prefill_varlen_fwd's packed, ragged batches.  Added under ABI
+ * version 4 beside an unchanged sfa_prefill_varlen_args: callers detect it by symbol.
+ * Every field of `args` keeps its sfa_prefill_varlen_fwd meaning -- layouts, strides, alignment, cu_seqlens read on the
+ * device only, total_q / total_k, head_dim 64 or 128, fp16 / bf16, GQA, exact scale -- and the workspace is that call's:
+ * sfa_prefill_varlen_workspace_bytes(batch, total_q) bytes, 256-byte aligned, the plan alone.  Except:
+ *   causal          must be non-zero, otherwise SFA_ERR_BAD_SHAPE: a two-sided window is not served.
+ *   window          >= 1 (window < 1 returns SFA_ERR_BAD_SHAPE).  In sequence b with n_q query rows and n_k key rows, with
+ *                   lim_i = i + (n_k - n_q) and lo_i = max(0, lim_i + 1 - window), query row i sees the keys [lo_i, lim_i]
+ *                   of its own sequence.  A window of n_k or more is the causal mask for that sequence (INT_MAX works).
+ *   sinks           device fp32 [heads_q], one logit per QUERY head, in natural-log units; it is NOT multiplied by
+ *                   softmax_scale.  4-byte aligned (checked: otherwise SFA_ERR_BAD_SHAPE).  Every value is finite or
+ *                   -inf (the caller's contract, not checked).  Read on the device only: a replayed graph sees new
+ *                   contents.  NULL: no sink.
+ * Semantics.  The o and lse rows of sequence b are what sfa_prefill_window_fwd gives for batch = 1, seqlen_q = n_q,
+ * seqlen_k = n_k on those rows -- bit for bit wherever that call runs its windowed kernel (sinks given, or window < n_k):
+ *   o   = sum_j exp(s_j) V_j / (exp(sinks[h]) + sum_j exp(s_j))
+ *   lse = log(exp(sinks[h]) + sum_j exp(s_j))
+ * over j in [lo_i, lim_i], s_j = q_i . k_j * softmax_scale.  A row without a visible key gets zeros and lse = -inf, sink
+ * or not: every row of a sequence with n_k == 0, and the rows with lim_i < 0 when n_q > n_k.  A sequence with n_q == 0
+ * takes no part; an invalid sequence is skipped with nothing of it read or written; there is no status word.
+ * What the call promises about memory: everything sfa_prefill_varlen_fwd promises, and with
+ * lo_0(b) = max(0, n_k - n_q + 1 - window), the bound of the sequence's first query row, no K or V row of sequence b
+ * below cu_k[b] + lo_0(b) is read; those rows may hold anything, NaN included.
+ * Argument checks: sfa_prefill_varlen_fwd's, in its order with its texts under this call's name.  Directly after the
+ * alignment step and before the batch == 0 or total_q == 0 return: sinks not 4-byte aligned, causal == 0, window < 1
+ * (SFA_ERR_BAD_SHAPE each).  The workspace checks and the grid check follow unchanged.
+ * Forwarding: with sinks == NULL and window >= total_k the call validates under its own name and then launches exactly
+ * what sfa_prefill_varlen_fwd(causal = 1) launches; the output is bit-identical to it.  Every other case -- window >=
+ * total_k with sinks included -- runs the plan kernel and csrc/prefill_varlen_window_kernel.hip's kernel.
+ * sfa_debug_get("last_prefill_kernel") and "last_prefill_splits" keep their values.  Like every entry point it is
+ * asynchronous on `stream`, allocates nothing, never synchronises and may be captured in a graph: two launches on the one
+ * stream, no parallel branches.
+ * Not served: head_dim 256; two-sided windows; soft-capping; a paged or fp8 K/V; a key-range split for packed batches; a
+ * status word for bad cu_seqlens; backward.
+ */
+int sfa_prefill_varlen_window_fwd(const sfa_prefill_varlen_args *args, int window, const float *sinks, void *workspace,
+                                  size_t workspace_bytes, void *stream);
 
 /* ---- test / A-B hooks: NOT part of the drop-in surface ------------------------------ */
 /* The launch paths read no environment variable; the test-suite and tools/ select kernel

@@ -290,9 +290,11 @@ std::vector<at::Tensor> mha_fwd_split(const at::Tensor &q, const at::Tensor &k, 
 // any token and head strides), cu_seqlens_q / cu_seqlens_k int32 [B + 1] on q's device, read there only
 // (include/star_flash_attn.h).  Returns [out] or [out, lse [Hq, Tq]].  The plan lives in the module's per-(device,
 // stream) workspace, behind its 256-byte status block.
-std::vector<at::Tensor> mha_varlen_fwd(const at::Tensor &q, const at::Tensor &k, const at::Tensor &v,
-                                       const at::Tensor &cu_seqlens_q, const at::Tensor &cu_seqlens_k, bool causal,
-                                       double softmax_scale, bool return_lse) {
+// (windowed: mha_varlen_fwd_window's call, with its window and sinks)
+static std::vector<at::Tensor> varlen_call(const at::Tensor &q, const at::Tensor &k, const at::Tensor &v,
+                                           const at::Tensor &cu_seqlens_q, const at::Tensor &cu_seqlens_k, bool causal,
+                                           double softmax_scale, bool return_lse, bool windowed, int64_t window,
+                                           const c10::optional<at::Tensor> &sinks_) {
     TORCH_CHECK(q.defined() && q.is_cuda(), "star_flash_attn: q must live on a HIP device");
     const int dt = dtype_code(q, "q");
     for (const at::Tensor *t : {&q, &k, &v}) {
@@ -310,6 +312,17 @@ std::vector<at::Tensor> mha_varlen_fwd(const at::Tensor &q, const at::Tensor &k,
                 " entries, cu_seqlens_k ", cu_seqlens_k.size(0));
     TORCH_CHECK(q.size(0) <= INT_MAX && k.size(0) <= INT_MAX && cu_seqlens_q.size(0) <= INT_MAX,
                 "star_flash_attn: too many rows");
+    const float *sinks = nullptr;
+    if (windowed) {
+        TORCH_CHECK(window >= 1 && window <= INT_MAX, "star_flash_attn: window must be in [1, INT_MAX], got ", window);
+        if (sinks_.has_value()) {
+            const at::Tensor &s = *sinks_;
+            TORCH_CHECK(s.is_cuda() && s.device() == q.device() && s.scalar_type() == at::kFloat && s.dim() == 1 &&
+                        s.size(0) == q.size(1) && s.is_contiguous(),
+                        "star_flash_attn: sinks must be a contiguous float32 [heads_q] tensor on q's device");
+            sinks = s.data_ptr<float>();
+        }
+    }
     at::Tensor out = at::empty_like(q, q.options(), at::MemoryFormat::Contiguous);
     at::Tensor lse;
     if (return_lse) lse = at::empty({q.size(1), q.size(0)}, q.options().dtype(at::kFloat));
@@ -332,9 +345,26 @@ std::vector<at::Tensor> mha_varlen_fwd(const at::Tensor &q, const at::Tensor &k,
     const size_t need = sfa_prefill_varlen_workspace_bytes(a.batch, a.total_q);
     void *ws = nullptr;
     if (need) ws = (char *)workspace(q.device(), stream, 256 + need).data_ptr() + 256;
-    check_status(sfa_prefill_varlen_fwd(&a, ws, need, stream), "mha_varlen_fwd");
+    if (windowed) check_status(sfa_prefill_varlen_window_fwd(&a, (int)window, sinks, ws, need, stream), "mha_varlen_fwd_window");
+    else check_status(sfa_prefill_varlen_fwd(&a, ws, need, stream), "mha_varlen_fwd");
     if (return_lse) return {out, lse};
     return {out};
+}
+
+std::vector<at::Tensor> mha_varlen_fwd(const at::Tensor &q, const at::Tensor &k, const at::Tensor &v,
+                                       const at::Tensor &cu_seqlens_q, const at::Tensor &cu_seqlens_k, bool causal,
+                                       double softmax_scale, bool return_lse) {
+    return varlen_call(q, k, v, cu_seqlens_q, cu_seqlens_k, causal, softmax_scale, return_lse, false, 0, c10::nullopt);
+}
+
+// mha_varlen_fwd under a sliding window (causal per sequence; row i sees the `window` keys of its own sequence that end
+// at its causal limit) with an optional attention sink per query head: sinks fp32 [Hq] on q's device
+// (include/star_flash_attn.h).
+std::vector<at::Tensor> mha_varlen_fwd_window(const at::Tensor &q, const at::Tensor &k, const at::Tensor &v,
+                                              const at::Tensor &cu_seqlens_q, const at::Tensor &cu_seqlens_k,
+                                              int64_t window, c10::optional<at::Tensor> sinks_, double softmax_scale,
+                                              bool return_lse) {
+    return varlen_call(q, k, v, cu_seqlens_q, cu_seqlens_k, true, softmax_scale, return_lse, true, window, sinks_);
 }
 
 std::vector<at::Tensor> compute_rotary_table(int max_seq_len, int rot_dim, at::ScalarType dtype, at::Device device) {
@@ -376,6 +406,11 @@ PYBIND11_MODULE(star_flash_attn, m) {
           "Attention forward (prefill) over packed sequences of different lengths: returns [out] or [out, lse]",
           py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cu_seqlens_q"), py::arg("cu_seqlens_k"),
           py::arg("causal") = false, py::arg("softmax_scale") = 0.0, py::arg("return_lse") = false);
+    m.def("mha_varlen_fwd_window", &mha_varlen_fwd_window,
+          "Attention forward (prefill) over packed sequences under a sliding window with optional attention sinks: "
+          "returns [out] or [out, lse]",
+          py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cu_seqlens_q"), py::arg("cu_seqlens_k"), py::arg("window"),
+          py::arg("sinks") = py::none(), py::arg("softmax_scale") = 0.0, py::arg("return_lse") = false);
     m.def("compute_rotary_table", &compute_rotary_table, "cos/sin LUT [max_seq_len, rot_dim/2]",
           py::arg("max_seq_len"), py::arg("rot_dim"), py::arg("dtype"), py::arg("device"));
 }

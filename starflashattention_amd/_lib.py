@@ -35,7 +35,7 @@ EXPORTED_SYMBOLS = [
     "sfa_decode_kv8_window_sinks", "sfa_decode_chunk_kv8_window_sinks", "sfa_decode_varlen_kv8_window_sinks",
     "sfa_prefill_window_fwd",
     "sfa_prefill_split_fwd", "sfa_prefill_split_workspace_bytes", "sfa_prefill_auto_splits",
-    "sfa_prefill_varlen_fwd", "sfa_prefill_varlen_workspace_bytes",
+    "sfa_prefill_varlen_fwd", "sfa_prefill_varlen_workspace_bytes", "sfa_prefill_varlen_window_fwd",
 ]
 
 
@@ -153,6 +153,9 @@ def load():
     lib.sfa_prefill_varlen_fwd.restype = ctypes.c_int
     lib.sfa_prefill_varlen_fwd.argtypes = [ctypes.POINTER(PrefillVarlenArgs), ctypes.c_void_p, ctypes.c_size_t,
                                            ctypes.c_void_p]
+    lib.sfa_prefill_varlen_window_fwd.restype = ctypes.c_int
+    lib.sfa_prefill_varlen_window_fwd.argtypes = [ctypes.POINTER(PrefillVarlenArgs), ctypes.c_int, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     lib.sfa_prefill_varlen_workspace_bytes.restype = ctypes.c_size_t
     lib.sfa_prefill_varlen_workspace_bytes.argtypes = [ctypes.c_int] * 2
     lib.sfa_compute_rotary_table.restype = ctypes.c_int

@@ -835,6 +835,81 @@ int split_auto(int batch, int heads_q, int seqlen_q, int seqlen_k) {
     return S < 2 ? 1 : split_resolve(nkt, (int)S);
 }
 
+// ---- sfa_prefill_varlen_fwd / sfa_prefill_varlen_window_fwd ----
+struct PrefillVarlenWindow { int window; const float *sinks; };     // what the windowed call adds to the checks
+
+// What the two packed prefill calls check and marshal alike, under the name of the call; w: the windowed call's
+// arguments, checked directly after the alignment step.  Returns a status; *launch is false where there is nothing to do
+// (batch or total_q of 0).
+int prefill_varlen_call(const char *name, const sfa_prefill_varlen_args *a, const PrefillVarlenWindow *w, void *workspace,
+                        size_t workspace_bytes, PrefillVarlenKernelParams *pp, bool *launch) {
+    *launch = false;
+    if (!a) return fail(SFA_ERR_NULL_POINTER, "%s: args is NULL", name);
+    if (!a->q || !a->k || !a->v || !a->o || !a->cu_seqlens_q || !a->cu_seqlens_k)
+        return fail(SFA_ERR_NULL_POINTER, "%s: q/k/v/o/cu_seqlens_q/cu_seqlens_k must be non-NULL", name);
+    if (a->batch < 0 || a->heads_q <= 0 || a->heads_kv <= 0 || a->total_q < 0 || a->total_k < 0)
+        return fail(SFA_ERR_BAD_SHAPE, "%s: batch=%d heads_q=%d heads_kv=%d total_q=%d total_k=%d", name, a->batch,
+                    a->heads_q, a->heads_kv, a->total_q, a->total_k);
+    if (a->heads_q % a->heads_kv)
+        return fail(SFA_ERR_BAD_SHAPE, "%s: heads_q=%d not a multiple of heads_kv=%d", name, a->heads_q, a->heads_kv);
+    if (a->head_dim != 64 && a->head_dim != 128)
+        return fail(SFA_ERR_UNSUPPORTED_HEAD_DIM, "%s: head_dim %d not in {64, 128}%s", name, a->head_dim,
+                    a->head_dim == 256 ? " (sfa_prefill_fwd serves head_dim 256)" : "");
+    if (a->dtype != SFA_DTYPE_FP16 && a->dtype != SFA_DTYPE_BF16)
+        return fail(SFA_ERR_BAD_DTYPE, "%s: dtype %d is not fp16(0)/bf16(1)", name, a->dtype);
+    const int64_t *st[4] = {a->q_stride, a->k_stride, a->v_stride, a->o_stride};
+    for (int t = 0; t < 4; ++t)
+        for (int i = 0; i < 2; ++i)
+            if (st[t][i] < 0 || (st[t][i] % 8) != 0)
+                return fail(SFA_ERR_BAD_SHAPE, "%s: strides must be >= 0 and multiples of 8 elements", name);
+    if (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->o) & 15)
+        return fail(SFA_ERR_BAD_SHAPE, "%s: tensors must be 16-byte aligned", name);
+    if (((uintptr_t)a->cu_seqlens_q | (uintptr_t)a->cu_seqlens_k | (uintptr_t)a->lse) & 3)
+        return fail(SFA_ERR_BAD_SHAPE, "%s: cu_seqlens_q, cu_seqlens_k and lse must be 4-byte aligned", name);
+    if (w) {
+        if ((uintptr_t)w->sinks & 3) return fail(SFA_ERR_BAD_SHAPE, "%s: sinks must be 4-byte aligned", name);
+        if (!a->causal)
+            return fail(SFA_ERR_BAD_SHAPE, "%s: causal must be non-zero (a two-sided window is not served)", name);
+        if (w->window < 1) return fail(SFA_ERR_BAD_SHAPE, "%s: window=%d must be >= 1", name, w->window);
+    }
+    if (a->batch == 0 || a->total_q == 0) return SFA_OK;
+    if (!workspace) return fail(SFA_ERR_NULL_POINTER, "%s: workspace is NULL", name);
+    if ((uintptr_t)workspace & 255) return fail(SFA_ERR_BAD_SHAPE, "%s: workspace must be 256-byte aligned", name);
+    const size_t need = sfa_prefill_varlen_workspace_bytes(a->batch, a->total_q);
+    if (workspace_bytes < need)
+        return fail(SFA_ERR_WORKSPACE_TOO_SMALL, "%s: workspace has %zu bytes, need %zu", name, workspace_bytes, need);
+    const long long bound = (long long)a->total_q / 256 + a->batch;
+    if (bound * a->heads_q > 0x7fffffffll) return fail(SFA_ERR_BAD_SHAPE, "%s: grid too large", name);
+
+    PrefillVarlenKernelParams &p = *pp;
+    memset(&p, 0, sizeof(p));
+    p.q = (const uint16_t *)a->q;
+    p.k = (const uint16_t *)a->k;
+    p.v = (const uint16_t *)a->v;
+    p.o = (uint16_t *)a->o;
+    p.lse = a->lse;
+    p.cu_q = (const int32_t *)a->cu_seqlens_q;
+    p.cu_k = (const int32_t *)a->cu_seqlens_k;
+    p.plan = (int2 *)workspace;
+    p.B = a->batch;
+    p.Hq = a->heads_q;
+    p.Hkv = a->heads_kv;
+    p.total_q = a->total_q;
+    p.total_k = a->total_k;
+    p.bound = (int)bound;
+    p.slices = a->heads_q % 8 == 0 ? 8 : 1;
+    for (int i = 0; i < 2; ++i) {
+        p.qs[i] = a->q_stride[i];
+        p.ks[i] = a->k_stride[i];
+        p.vs[i] = a->v_stride[i];
+        p.os[i] = a->o_stride[i];
+    }
+    const float scale = a->softmax_scale > 0.f ? a->softmax_scale : 1.0f / std::sqrt((float)a->head_dim);
+    p.scale_log2 = scale * 1.4426950408889634f;
+    *launch = true;
+    return SFA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -908,64 +983,30 @@ size_t sfa_prefill_varlen_workspace_bytes(int batch, int total_q) {
 }
 
 int sfa_prefill_varlen_fwd(const sfa_prefill_varlen_args *a, void *workspace, size_t workspace_bytes, void *stream) {
-    static const char *const name = "sfa_prefill_varlen_fwd";
-    if (!a) return fail(SFA_ERR_NULL_POINTER, "%s: args is NULL", name);
-    if (!a->q || !a->k || !a->v || !a->o || !a->cu_seqlens_q || !a->cu_seqlens_k)
-        return fail(SFA_ERR_NULL_POINTER, "%s: q/k/v/o/cu_seqlens_q/cu_seqlens_k must be non-NULL", name);
-    if (a->batch < 0 || a->heads_q <= 0 || a->heads_kv <= 0 || a->total_q < 0 || a->total_k < 0)
-        return fail(SFA_ERR_BAD_SHAPE, "%s: batch=%d heads_q=%d heads_kv=%d total_q=%d total_k=%d", name, a->batch,
-                    a->heads_q, a->heads_kv, a->total_q, a->total_k);
-    if (a->heads_q % a->heads_kv)
-        return fail(SFA_ERR_BAD_SHAPE, "%s: heads_q=%d not a multiple of heads_kv=%d", name, a->heads_q, a->heads_kv);
-    if (a->head_dim != 64 && a->head_dim != 128)
-        return fail(SFA_ERR_UNSUPPORTED_HEAD_DIM, "%s: head_dim %d not in {64, 128}%s", name, a->head_dim,
-                    a->head_dim == 256 ? " (sfa_prefill_fwd serves head_dim 256)" : "");
-    if (a->dtype != SFA_DTYPE_FP16 && a->dtype != SFA_DTYPE_BF16)
-        return fail(SFA_ERR_BAD_DTYPE, "%s: dtype %d is not fp16(0)/bf16(1)", name, a->dtype);
-    const int64_t *st[4] = {a->q_stride, a->k_stride, a->v_stride, a->o_stride};
-    for (int t = 0; t < 4; ++t)
-        for (int i = 0; i < 2; ++i)
-            if (st[t][i] < 0 || (st[t][i] % 8) != 0)
-                return fail(SFA_ERR_BAD_SHAPE, "%s: strides must be >= 0 and multiples of 8 elements", name);
-    if (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->o) & 15)
-        return fail(SFA_ERR_BAD_SHAPE, "%s: tensors must be 16-byte aligned", name);
-    if (((uintptr_t)a->cu_seqlens_q | (uintptr_t)a->cu_seqlens_k | (uintptr_t)a->lse) & 3)
-        return fail(SFA_ERR_BAD_SHAPE, "%s: cu_seqlens_q, cu_seqlens_k and lse must be 4-byte aligned", name);
-    if (a->batch == 0 || a->total_q == 0) return SFA_OK;
-    if (!workspace) return fail(SFA_ERR_NULL_POINTER, "%s: workspace is NULL", name);
-    if ((uintptr_t)workspace & 255) return fail(SFA_ERR_BAD_SHAPE, "%s: workspace must be 256-byte aligned", name);
-    const size_t need = sfa_prefill_varlen_workspace_bytes(a->batch, a->total_q);
-    if (workspace_bytes < need)
-        return fail(SFA_ERR_WORKSPACE_TOO_SMALL, "%s: workspace has %zu bytes, need %zu", name, workspace_bytes, need);
-    const long long bound = (long long)a->total_q / 256 + a->batch;
-    if (bound * a->heads_q > 0x7fffffffll) return fail(SFA_ERR_BAD_SHAPE, "%s: grid too large", name);
-
     PrefillVarlenKernelParams p;
-    memset(&p, 0, sizeof(p));
-    p.q = (const uint16_t *)a->q;
-    p.k = (const uint16_t *)a->k;
-    p.v = (const uint16_t *)a->v;
-    p.o = (uint16_t *)a->o;
-    p.lse = a->lse;
-    p.cu_q = (const int32_t *)a->cu_seqlens_q;
-    p.cu_k = (const int32_t *)a->cu_seqlens_k;
-    p.plan = (int2 *)workspace;
-    p.B = a->batch;
-    p.Hq = a->heads_q;
-    p.Hkv = a->heads_kv;
-    p.total_q = a->total_q;
-    p.total_k = a->total_k;
-    p.bound = (int)bound;
-    p.slices = a->heads_q % 8 == 0 ? 8 : 1;
-    for (int i = 0; i < 2; ++i) {
-        p.qs[i] = a->q_stride[i];
-        p.ks[i] = a->k_stride[i];
-        p.vs[i] = a->v_stride[i];
-        p.os[i] = a->o_stride[i];
-    }
-    const float scale = a->softmax_scale > 0.f ? a->softmax_scale : 1.0f / std::sqrt((float)a->head_dim);
-    p.scale_log2 = scale * 1.4426950408889634f;
+    bool launch;
+    if (const int rc = prefill_varlen_call("sfa_prefill_varlen_fwd", a, nullptr, workspace, workspace_bytes, &p, &launch))
+        return rc;
+    if (!launch) return SFA_OK;
     return launch_prefill_varlen(p, a->dtype, a->head_dim, a->causal != 0, (hipStream_t)stream);
+}
+
+// sfa_prefill_varlen_fwd under a sliding window, with an optional attention sink per query head.  No sink and a window
+// that covers every key of the batch: the call is sfa_prefill_varlen_fwd's (causal), launch and all
+int sfa_prefill_varlen_window_fwd(const sfa_prefill_varlen_args *a, int window, const float *sinks, void *workspace,
+                                  size_t workspace_bytes, void *stream) {
+    PrefillVarlenWindowKernelParams wp;
+    const PrefillVarlenWindow w{window, sinks};
+    bool launch;
+    if (const int rc = prefill_varlen_call("sfa_prefill_varlen_window_fwd", a, &w, workspace, workspace_bytes, &wp.base,
+                                           &launch))
+        return rc;
+    if (!launch) return SFA_OK;
+    if (!sinks && window >= a->total_k) return launch_prefill_varlen(wp.base, a->dtype, a->head_dim, true, (hipStream_t)stream);
+    const int cap = a->total_k > 1 ? a->total_k : 1;    // a longer window is the causal mask of every sequence
+    wp.window = window < cap ? window : cap;
+    wp.sinks = sinks;
+    return launch_prefill_varlen_window(wp, a->dtype, a->head_dim, (hipStream_t)stream);
 }
 
 int sfa_prefill_fwd(const sfa_prefill_args *a, void *stream) {

@@ -1,35 +1,27 @@
-// Prefill forward over packed sequences of different lengths for gfx950 (MI355X): sfa_prefill_varlen_fwd.
-// bf16 / fp16, head_dim 64 / 128, causal (bottom-right aligned per sequence) or full, MHA or GQA, q / o [total_q, Hq, D] and
+// Prefill forward over packed sequences of different lengths with a sliding window and an optional attention sink for
+// gfx950 (MI355X): sfa_prefill_varlen_window_fwd.
+// bf16 / fp16, head_dim 64 / 128, causal (bottom-right aligned per sequence), MHA or GQA, q / o [total_q, Hq, D] and
 // k / v [total_k, Hkv, D] with any token and head strides; sequence b owns the rows [cu_q[b], cu_q[b+1]) and
 // [cu_k[b], cu_k[b+1]).
 //
-// Two kernels on one stream:
-//   prefill_varlen_plan_kernel  one workgroup: from cu_seqlens_q / cu_seqlens_k the compact list of (sequence, q-tile)
-//                               work items -- ceil(n_q / 256) per valid sequence with rows, a sequence's last q-tile
-//                               first (the heaviest under the causal mask) -- padded with the empty marker (-1, 0) up to
-//                               bound = total_q / 256 + B slots (every sequence with rows has ceil(n_q / 256) <=
-//                               n_q / 256 + 1 q-tiles); items past the bound are dropped.  decode_varlen_geo.h's pattern:
-//                               no host synchronisation, every slot written on every call.
-//   prefill_varlen_kernel       one workgroup per (plan slot, query head): the whole key range [0, nkt(qt)) of the
-//                               sequence for one q-tile, o and lse written in place.
-// The tile pipeline is prefill_split_kernel.hip's walk of [ts0, wg_end) with ts0 = 0 (design notes: prefill_kernel.hip): a
-// q-tile of 256 query rows, 8 waves of 32 rows, 64-key K/V tiles staged through registers into triple-buffered padded
-// LDS images with one barrier per tile, and prefill_core.h's slot-ordered half-step h_block at exact scale (ORD 2, PF 2).
-// The staging scaffold is a copy of that file's; the epilogue is prefill_window_kernel.hip's without the sink.  What
-// differs:
-//   * The workgroup reads its plan item and its sequence's four cu entries with wave-uniform loads, leaves on the marker
-//     before any barrier, and re-derives the sequence's validity (0 <= cu[b] <= cu[b+1] <= total in both arrays): the
-//     kernel is safe for any cu contents, and an invalid sequence is neither read nor written.
-//   * Sq, Sk and the causal offset are the sequence's own; the base pointers are cu * token stride in 64 bits; the lse
-//     row is h * total_q + cu_q[b] + row.
-//   * Never read: the ragged last key tile clamps its rows to the sequence's own last key, the ragged last q-tile to its
-//     own last row -- never into the next sequence's rows.  A stream position past the end re-reads the last tile.
-//   * A sequence with no keys (or a q-tile whose rows all lie above the causal limit) stages nothing: the epilogue
-//     writes zeros and lse = -inf from the empty accumulator.
-// blockIdx -> (plan slot, head): the plan slot is the slow digit, so every real workgroup is launched before the first
-// empty one (decode_varlen_kernel.hip measured why).  With Hq % 8 == 0, blockIdx & 7 selects a slice of Hq / 8 query
-// heads (XCD x under round-robin dispatch; a speed hint only) and blockIdx >> 3 = slot * (Hq / 8) + head in slice: the
-// q-tiles of one (sequence, kv head) meet on one XCD's L2.  Otherwise blockIdx = slot * Hq + head.
+// Two kernels on one stream: prefill_varlen_kernel.hip's plan kernel (launch_prefill_varlen_plan), then
+// prefill_varlen_window_kernel, one workgroup per (plan slot, query head).  The attention kernel is
+// prefill_varlen_kernel's work-item front end joined to prefill_window_kernel's walk and epilogue (design notes in those
+// two files and in prefill_kernel.hip); the staging scaffold is a copy of theirs.
+//   * From prefill_varlen_kernel: the plan slot and head from blockIdx, the four wave-uniform cu loads, leaving on the
+//     marker or on an invalid sequence before any barrier (safe for any cu contents: an invalid sequence is neither read
+//     nor written), 64-bit base pointers cu * token stride, the lse row h * total_q + cu_q[b] + row.
+//   * From prefill_window_kernel: the tiles [ts0, wg_end) of the q-tile, the wave's own [tw0, ntw) with leading and
+//     trailing idle steps, mask_bits with the wave's largest lower bound, the LowMask hook, the first-tile and last-tile
+//     clamps through one min(max(row, first), last), and the sink folded once in the epilogue into rows that have a key.
+//   * Every quantity is the sequence's own: Sq = n_q, Sk = n_k, coff = n_k - n_q (negative when n_q > n_k: the rows with
+//     lim < 0 have no key, and a q-tile of such rows stages nothing and writes zeros and -inf from the empty accumulator,
+//     sink or not), lo_0 = max(0, n_k - n_q + 1 - window) relative to the sequence's first key.  The walk is the
+//     rectangular kernel's step for step, so a sequence's rows carry that kernel's bits.
+//   * Never read: K and V rows of the sequence below lo_0 (the tile that holds lo_0 clamps its rows up to it; it may be
+//     the ragged last tile too, n_k = 65 with lo_0 = 64: both clamps apply), rows past the sequence's last key or last
+//     query row, and everything of another sequence.
+// blockIdx -> (plan slot, head) is prefill_varlen_kernel.hip's map.
 #include "prefill_core.h"
 #include "prefill_varlen_seq.h"
 
@@ -39,44 +31,16 @@ namespace {
 
 using namespace prefill;
 
-// plan[i] = (b, q_tile) for the i-th work item, (-1, 0) from the last item up to p.bound.  One workgroup walks the
-// sequences 256 at a time: tile counts, an inclusive scan in LDS, then every thread writes its sequence's items.  (The
-// scan is 64 bit: 256 sequences of garbage cu contents may each claim total_q / 256 + 1 tiles.)
-__global__ void __launch_bounds__(256)
-prefill_varlen_plan_kernel(const PrefillVarlenKernelParams p) {
-    __shared__ long long scan[256];
-    __shared__ int base_s;
-    const int tid = threadIdx.x;
-    if (tid == 0) base_s = 0;
-    __syncthreads();
-    for (int b0 = 0; b0 < p.B; b0 += 256) {
-        const int b = b0 + tid;
-        int tiles = 0;
-        if (b < p.B) {
-            int q0, q1, k0, k1;
-            if (varlen_seq(p, b, q0, q1, k0, k1)) tiles = (q1 - q0 + kBM - 1) / kBM;
-        }
-        scan[tid] = tiles;
-        __syncthreads();
-        for (int d = 1; d < 256; d <<= 1) {     // inclusive Hillis-Steele scan
-            const long long add = tid >= d ? scan[tid - d] : 0;
-            __syncthreads();
-            scan[tid] += add;
-            __syncthreads();
-        }
-        const int base = base_s;
-        const long long first = base + scan[tid] - tiles;
-        for (int i = 0; i < tiles && first + i < p.bound; ++i) p.plan[first + i] = make_int2(b, tiles - 1 - i);
-        __syncthreads();
-        if (tid == 255) base_s = (int)min(base + scan[255], (long long)p.bound);
-        __syncthreads();
-    }
-    for (int i = base_s + tid; i < p.bound; i += 256) p.plan[i] = make_int2(-1, 0);
+// The window's lower mask of a half-tile of fresh scores (mask_half's register layout): keys below lo get -inf
+__device__ __forceinline__ void mask_below(f32x16 &s, int kbase, int h2, int lo) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+        if (kbase + (r & 3) + 8 * (r >> 2) + 4 * h2 < lo) s[r] = ninf();
 }
 
-template <class Tr, int D, bool CAUSAL>
+template <class Tr, int D, bool SINK>
 __global__ void __launch_bounds__(kThreads, 2)
-prefill_varlen_kernel(const PrefillVarlenKernelParams p) {
+prefill_varlen_window_kernel(const PrefillVarlenWindowKernelParams wp) {
     using Vec = typename Tr::mfma_vec;
     constexpr int NQB = 1, PF = 2, ORD = 2;     // one 32-row query block per wave, exact scale, staged softmax
     constexpr int NKS = D / 16;                 // k-steps of Q.K^T
@@ -88,6 +52,7 @@ prefill_varlen_kernel(const PrefillVarlenKernelParams p) {
     using L = Lds<D>;
     static_assert(NLD >= 1 && NLD <= 2, "staging registers are named kr0, kr1");
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    const PrefillVarlenKernelParams &p = wp.base;
 
     // ---- the work item: plan slot on the slow digit, the head slice on the fast one (all of it workgroup-uniform) ----
     const int hps = p.Hq / p.slices;            // query heads per slice
@@ -105,29 +70,36 @@ prefill_varlen_kernel(const PrefillVarlenKernelParams p) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // provably wave-uniform
     const int l31 = lane & 31, h2 = lane >> 5;
-    const int coff = Sk - Sq;                   // causal: key j visible to row i iff j <= i + coff
+    const int coff = Sk - Sq;                   // key j visible to row i iff lo_i <= j <= i + coff (may be negative)
     const int q0 = qt * kBM, wq0 = q0 + 32 * wave, qrow = wq0 + l31;
 
-    // ---- the key range of this workgroup: tiles [0, wg_end), the whole range the q-tile's last row sees ----
-    constexpr int ts0 = 0;
-    const int n_kv_tiles = (Sk + kBN - 1) / kBN;
-    int wg_end = n_kv_tiles;
-    if (CAUSAL) {
-        const int rlim = min(q0 + kBM, Sq) - 1 + coff;      // (<= Sk - 1)
-        wg_end = rlim < 0 ? 0 : rlim / kBN + 1;
-    }
-    const int nt = wg_end;                      // tiles the workgroup stages (workgroup-uniform); 0: no visible key
+    // ---- the key range of this workgroup: tiles [ts0, wg_end) of the sequence ----
+    // 1 <= win <= max(Sk, 1): a window longer than the sequence is the causal mask (lo = 0 for every row).  Every limit is
+    // a row of the sequence plus coff, in (-total_q, total_k): limit >= win >= 1 keeps limit + 1 - win in [1, limit].
+    const int win = min(wp.window, max(Sk, 1));
+    auto low_of = [&](int limit) -> int { return limit < win ? 0 : limit + 1 - win; };
+    const int lo0 = low_of(coff);               // no row sees a key below the first row's lower bound
+    const int tlo = lo0 / kBN;
+    const int rlast = min(q0 + kBM, Sq) - 1;    // last query row of the q-tile
+    const int ts0 = low_of(q0 + coff) / kBN;
+    const int wg_end = rlast + coff >= 0 ? (rlast + coff) / kBN + 1 : 0;    // (lim <= Sk - 1 for every row)
+    const int nt = max(0, wg_end - ts0);        // tiles the workgroup stages (workgroup-uniform); 0: no visible key
     const int wlast = min(wq0 + 31, Sq - 1);    // last query row of the wave
-    int ntw = 0;                                // end of the tiles this wave computes on (wave-uniform)
-    if (wq0 < Sq) {
-        if (!CAUSAL) ntw = nt;
-        else if (wlast + coff >= 0) ntw = min(wg_end, (wlast + coff) / kBN + 1);
-    }
+    int ntw = 0;                                // end of the tiles this wave computes on, from ts0 (wave-uniform)
+    if (wq0 < Sq && wlast + coff >= 0) ntw = max(0, min(wg_end, (wlast + coff) / kBN + 1) - ts0);
     int lim[NQB];                               // last visible key of this lane's row (< 0: none)
-    lim[0] = CAUSAL ? min(qrow, Sq - 1) + coff : Sk - 1;
-    const int wlim = CAUSAL ? wq0 + coff : Sk - 1;      // the smallest limit of the wave's rows
+    lim[0] = min(qrow, Sq - 1) + coff;
+    const int wlim = wq0 + coff;                // the smallest limit of the wave's rows
+    // this lane's lower bound, the largest one of the wave's rows, and the leading tiles of the workgroup that lie wholly
+    // below the smallest one
+    const int lo_r = low_of(lim[0]);
+    const int wlo = low_of(wlast + coff);
+    const int tw0 = min(max(0, low_of(wlim) / kBN - ts0), ntw);
     // bit 0 set: the 32 keys starting at KBASE need masking for this wave's rows
-    auto mask_bits = [&](int kbase) -> int { return kbase + 31 > wlim ? 1 : 0; };
+    auto mask_bits = [&](int kbase) -> int { return (kbase + 31 > wlim || kbase < wlo) ? 1 : 0; };
+    auto low_mask = [&](f32x16 &s, int kbase, int) {
+        if (kbase < wlo) mask_below(s, kbase, h2, lo_r);
+    };
 
     // ---- staging: thread owns chunks (row st_row + i*ROWSTEP, chunk st_ch), i < NLD, of every tile ----
     const int st_row = tid / CPR, st_ch = tid % CPR;
@@ -141,26 +113,32 @@ prefill_varlen_kernel(const PrefillVarlenKernelParams p) {
     kr0 = kr1 = vr0 = vr1 = make_uint4(0, 0, 0, 0);
 
     // Rows of a tile: row r is at r * row bytes from the tile's base.  The ragged last tile (Sk % 64 != 0) clamps its
-    // rows to the sequence's last key: nothing past it -- the next sequence's first rows -- is read.
+    // rows to the sequence's last key, the tile that holds lo0 to the first valid one: nothing below lo0 and nothing past
+    // the sequence's last key -- the next sequence's first rows -- is read.  (One tile may be both.)
+    const int n_kv_tiles = (Sk + kBN - 1) / kBN;
     const int ragged_tile = (Sk % kBN) ? n_kv_tiles - 1 : -1;
     const int last0 = Sk - 1 - (n_kv_tiles - 1) * kBN;      // last valid row of the last tile
+    const int first0 = lo0 - tlo * kBN;                     // first valid row of the first tile
     const int row0_ = st_row, row1_ = st_row + ROWSTEP;
     const unsigned ch_off = 16u * st_ch;
     constexpr int NOPS = 2 * NLD;   // op n: even = K chunk n/2, odd = V chunk n/2
     // where the K and V tiles of two stream positions live and which of their rows exist: once per step, scalar
-    struct TileSrc { const char *k, *v; int lk, lv; };
+    struct TileSrc { const char *k, *v; int fk, lk, fv, lv; };
     auto tile_of = [&](int pos) -> int { return min(ts0 + pos, wg_end - 1); };     // past the end: re-read the last tile
     auto tile_src = [&](int pos_k, int pos_v) -> TileSrc {
         const int tk = tile_of(pos_k), tv = tile_of(pos_v);
         return TileSrc{kg + tk * k_tile_bytes, vg + tv * v_tile_bytes,
-                       tk == ragged_tile ? last0 : kBN - 1, tv == ragged_tile ? last0 : kBN - 1};
+                       tk == tlo ? first0 : 0, tk == ragged_tile ? last0 : kBN - 1,
+                       tv == tlo ? first0 : 0, tv == ragged_tile ? last0 : kBN - 1};
     };
-    auto row_off = [&](int row, int last, unsigned rowb) -> unsigned { return (unsigned)min(row, last) * rowb + ch_off; };
+    auto row_off = [&](int row, int first, int last, unsigned rowb) -> unsigned {
+        return (unsigned)min(max(row, first), last) * rowb + ch_off;
+    };
     auto ld_k = [&](const TileSrc &ts, int i) -> uint4 {
-        return *reinterpret_cast<const uint4 *>(ts.k + row_off(i == 0 ? row0_ : row1_, ts.lk, k_rowb));
+        return *reinterpret_cast<const uint4 *>(ts.k + row_off(i == 0 ? row0_ : row1_, ts.fk, ts.lk, k_rowb));
     };
     auto ld_v = [&](const TileSrc &ts, int i) -> uint4 {
-        return *reinterpret_cast<const uint4 *>(ts.v + row_off(i == 0 ? row0_ : row1_, ts.lv, v_rowb));
+        return *reinterpret_cast<const uint4 *>(ts.v + row_off(i == 0 ? row0_ : row1_, ts.fv, ts.lv, v_rowb));
     };
     auto load_op = [&](int n, const TileSrc &ts) {
         if (n == 0) kr0 = ld_k(ts, 0);
@@ -251,6 +229,11 @@ prefill_varlen_kernel(const PrefillVarlenKernelParams p) {
         Vec kpre[PF];                                       // first PF K fragments of the next half-step
 #pragma unroll
         for (int i = 0; i < PF; ++i) kpre[i] = bitcast<Vec>(make_uint4(0, 0, 0, 0));
+        // ---- leading idle steps: tiles below every row of this wave ----
+        for (; t < tw0; ++t) {
+            SFA_STAGE_AND_SYNC(t);
+            SFA_ADVANCE();
+        }
         // ---- scores of the first half-tile, first fragments of the second ----
         if (t < ntw) {
 #pragma unroll
@@ -276,7 +259,7 @@ prefill_varlen_kernel(const PrefillVarlenKernelParams p) {
                 for (int n = j * NOPS / NPV_; n < (j + 1) * NOPS / NPV_; ++n) store_op(n, k2, v1);
             };
             h_block<Tr, D, NQB, PF, ORD, 1, 0, true, true>(kb, vb, kb1, qf, sB, sA, acc, c2, mxA, mxB,
-                                                           mask_bits(kbase), kbase, h2, lim, kpre, NoHook(), st_hook);
+                                                           mask_bits(kbase), kbase, h2, lim, kpre, NoHook(), st_hook, low_mask);
             __syncthreads();
             const TileSrc ts = tile_src(t + 3, t + 2);
             auto ld_hook = [&](int i) {         // NOPS loads spread evenly over QK slots 1..NKS-1
@@ -284,7 +267,7 @@ prefill_varlen_kernel(const PrefillVarlenKernelParams p) {
                 for (int n = (i - 1) * NOPS / (NKS - 1); n < i * NOPS / (NKS - 1); ++n) load_op(n, ts);
             };
             h_block<Tr, D, NQB, PF, ORD, 0, 1, true, true>(kb1, vb, kb1, qf, sA, sB, acc, c2, mxB, mxA,
-                                                           mask_bits(kbase + 32), kbase + 32, h2, lim, kpre, ld_hook, NoHook());
+                                                           mask_bits(kbase + 32), kbase + 32, h2, lim, kpre, ld_hook, NoHook(), low_mask);
             SFA_ADVANCE();
         }
         // ---- TAIL step: this wave's last tile (its second half computes no new scores) ----
@@ -292,10 +275,11 @@ prefill_varlen_kernel(const PrefillVarlenKernelParams p) {
             const char *kb = k_rd + kcur, *vb = v_rd + vcur;
             const int kbase = (ts0 + t) * kBN;
             h_block<Tr, D, NQB, PF, ORD, 1, 0, true, false>(kb, vb, kb, qf, sB, sA, acc, c2, mxA, mxB,
-                                                            mask_bits(kbase), kbase, h2, lim, kpre, NoHook(), NoHook());
+                                                            mask_bits(kbase), kbase, h2, lim, kpre, NoHook(), NoHook(), low_mask);
             SFA_STAGE_AND_SYNC(t);
             h_block<Tr, D, NQB, PF, ORD, 0, 1, false, false>(kb, vb, kb, qf, sA, sB, acc, c2, mxB, mxA,
-                                                             mask_bits(kbase + 32), kbase + 32, h2, lim, kpre, NoHook(), NoHook());
+                                                             mask_bits(kbase + 32), kbase + 32, h2, lim, kpre, NoHook(), NoHook(),
+                                                             low_mask);
             SFA_ADVANCE();
             ++t;
         }
@@ -309,8 +293,27 @@ prefill_varlen_kernel(const PrefillVarlenKernelParams p) {
 #undef SFA_STAGE_AND_SYNC
     }
 
-    // ---- epilogue: normalise, convert, store O[row][:] and lse; a row with no visible key gets zeros and -inf ----
-    const float ltot = half_sum(acc.lsum[0]);
+    // ---- epilogue: fold the sink, normalise, convert, store O[row][:] and lse; a row with no visible key gets zeros
+    // and -inf ----
+    float ltot = half_sum(acc.lsum[0]);
+    // SINK: one more stream element of the row -- max sinks[h] log2(e), sum 1, accumulator 0 -- folded in once.  A row
+    // with no visible key (ltot == 0) stays empty: the sink joins only a softmax that has a key.
+    if constexpr (SINK) {
+        // (laundered: contracted into `sk - ms` below as one fma, the product's rounding error would stand where 0
+        // belongs when the sink is the max)
+        float sk = wp.sinks[h] * 1.4426950408889634f;
+        asm volatile("" : "+v"(sk));
+        const bool has = ltot > 0.f;
+        const float mn = fmaxf(acc.msc[0], sk);
+        const float ms = (mn == ninf()) ? 0.f : mn;
+        const float a1 = fast_exp2(acc.msc[0] - ms);
+#pragma unroll
+        for (int d = 0; d < NDB; ++d)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc.o[0][d][r] *= a1;
+        ltot = has ? __builtin_fmaf(ltot, a1, fast_exp2(sk - ms)) : 0.f;
+        acc.msc[0] = has ? mn : acc.msc[0];
+    }
     const float inv = ltot > 0.f ? 1.0f / ltot : 0.f;
     if (qrow < Sq) {
         uint16_t *orow = p.o + ((long long)cq0 + qrow) * p.os[0] + h * p.os[1];
@@ -322,35 +325,30 @@ prefill_varlen_kernel(const PrefillVarlenKernelParams p) {
     }
 }
 
-template <class Tr, int D, bool CAUSAL>
-int launch_t(const PrefillVarlenKernelParams &p, hipStream_t stream) {
+template <class Tr, int D, bool SINK>
+int launch_t(const PrefillVarlenWindowKernelParams &p, hipStream_t stream) {
     const size_t lds = Lds<D>::TOTAL;          // K[3] + V[3], padded rows
-    dim3 grid((unsigned)p.bound * (unsigned)p.Hq), block(kThreads);     // (checked by the caller)
+    dim3 grid((unsigned)p.base.bound * (unsigned)p.base.Hq), block(kThreads);     // (checked by the caller)
     static DynLdsAttr attr;
-    if (const int rc = attr.ensure(reinterpret_cast<const void *>(&prefill_varlen_kernel<Tr, D, CAUSAL>), (int)lds,
-                                   "prefill_varlen_kernel"))
+    if (const int rc = attr.ensure(reinterpret_cast<const void *>(&prefill_varlen_window_kernel<Tr, D, SINK>), (int)lds,
+                                   "prefill_varlen_window_kernel"))
         return rc;
-    hipLaunchKernelGGL((prefill_varlen_kernel<Tr, D, CAUSAL>), grid, block, lds, stream, p);
-    return check_launch("prefill_varlen_kernel");
+    hipLaunchKernelGGL((prefill_varlen_window_kernel<Tr, D, SINK>), grid, block, lds, stream, p);
+    return check_launch("prefill_varlen_window_kernel");
 }
 
 template <class Tr, int D>
-int launch_c(const PrefillVarlenKernelParams &p, bool causal, hipStream_t stream) {
-    return causal ? launch_t<Tr, D, true>(p, stream) : launch_t<Tr, D, false>(p, stream);
+int launch_d(const PrefillVarlenWindowKernelParams &p, hipStream_t stream) {
+    return p.sinks ? launch_t<Tr, D, true>(p, stream) : launch_t<Tr, D, false>(p, stream);
 }
 
 }  // namespace
 
-int launch_prefill_varlen_plan(const PrefillVarlenKernelParams &p, hipStream_t stream) {
-    hipLaunchKernelGGL(prefill_varlen_plan_kernel, dim3(1), dim3(256), 0, stream, p);
-    return check_launch("prefill_varlen_plan_kernel");
-}
-
-int launch_prefill_varlen(const PrefillVarlenKernelParams &p, int dtype, int head_dim, bool causal, hipStream_t stream) {
-    if (const int rc = launch_prefill_varlen_plan(p, stream)) return rc;
+int launch_prefill_varlen_window(const PrefillVarlenWindowKernelParams &p, int dtype, int head_dim, hipStream_t stream) {
+    if (const int rc = launch_prefill_varlen_plan(p.base, stream)) return rc;
     const bool h = dtype == SFA_DTYPE_FP16;
-    if (head_dim == 64) return h ? launch_c<Fp16, 64>(p, causal, stream) : launch_c<Bf16, 64>(p, causal, stream);
-    return h ? launch_c<Fp16, 128>(p, causal, stream) : launch_c<Bf16, 128>(p, causal, stream);
+    if (head_dim == 64) return h ? launch_d<Fp16, 64>(p, stream) : launch_d<Bf16, 64>(p, stream);
+    return h ? launch_d<Fp16, 128>(p, stream) : launch_d<Bf16, 128>(p, stream);
 }
 
 }  // namespace sfa

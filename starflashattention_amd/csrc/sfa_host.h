@@ -221,6 +221,14 @@ struct PrefillVarlenKernelParams {
     float scale_log2;
 };
 
+// sfa_prefill_varlen_window_fwd (prefill_varlen_window_kernel.hip): the packed prefill forward with a sliding window and
+// an optional attention sink, per sequence.  Window and sink ride behind the unchanged parameters, as above.
+struct PrefillVarlenWindowKernelParams {
+    PrefillVarlenKernelParams base;     // every field keeps its meaning
+    int window;             // >= 1: row i of a sequence with causal limit lim sees its keys max(0, lim + 1 - window) .. lim
+    const float *sinks;     // [Hq] fp32, one logit per query head (natural-log units, not scaled), or nullptr
+};
+
 int launch_decode(const DecodeKernelParams &p, int dtype, int head_dim, hipStream_t stream);     // decode_dispatch.hip
 // non-temporal cache loads? (both caches of elem_bytes per element against the Infinity Cache, or the decode_nt knob)
 bool decode_nt(const DecodeKernelParams &p, int head_dim, int elem_bytes);                       // decode_dispatch.hip
@@ -270,9 +278,15 @@ int launch_prefill_window(const PrefillWindowKernelParams &p, int dtype, int hea
 int launch_prefill_split(const PrefillSplitKernelParams &p, int dtype, int head_dim, bool causal, hipStream_t stream);
 int launch_prefill_split_combine(const PrefillSplitKernelParams &p, int dtype, int head_dim, bool causal,
                                  hipStream_t stream);
-// prefill_varlen_kernel.hip: called by sfa_prefill_varlen_fwd only (validated dtype, head_dim 64 / 128, B > 0, total_q >
-// 0): the plan kernel, then the attention kernel over the plan, on the same stream
+// prefill_varlen_kernel.hip: called by sfa_prefill_varlen_fwd, and by sfa_prefill_varlen_window_fwd where it forwards
+// (validated dtype, head_dim 64 / 128, B > 0, total_q > 0): the plan kernel, then the attention kernel over the plan, on
+// the same stream
 int launch_prefill_varlen(const PrefillVarlenKernelParams &p, int dtype, int head_dim, bool causal, hipStream_t stream);
+// prefill_varlen_kernel.hip: the plan kernel alone (every slot of p.plan written), for the packed kernels of other units
+int launch_prefill_varlen_plan(const PrefillVarlenKernelParams &p, hipStream_t stream);
+// prefill_varlen_window_kernel.hip: called by sfa_prefill_varlen_window_fwd only (validated as above, window >= 1): the
+// plan kernel, then the windowed attention kernel over the plan, on the same stream
+int launch_prefill_varlen_window(const PrefillVarlenWindowKernelParams &p, int dtype, int head_dim, hipStream_t stream);
 int launch_rotary_table(void *cos_t, void *sin_t, int max_seq_len, int rot_dim, int dtype, hipStream_t stream);
 int launch_fill16(void *arr, uint16_t bits, size_t n, hipStream_t stream);
 

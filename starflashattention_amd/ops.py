@@ -690,17 +690,10 @@ def prefill_varlen_workspace_bytes(batch, total_q):
     return _lib.load().sfa_prefill_varlen_workspace_bytes(int(batch), int(total_q))
 
 
-def flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, causal=False, softmax_scale=None, out=None,
-                          return_lse=False, workspace=None):
-    """flash_attn_fwd over packed sequences of different lengths (sfa_prefill_varlen_fwd).  q [Tq, Hq, D], k / v
-    [Tk, Hkv, D] with any token and head strides and D contiguous, fp16 or bf16, D in {64, 128}; cu_seqlens_q /
-    cu_seqlens_k int32 [B + 1] tensors on q's device: sequence b owns the query rows [cu_q[b], cu_q[b+1]) and the key rows
-    [cu_k[b], cu_k[b+1]) and gets what flash_attn_fwd gives for those rows alone (causal: bottom-right aligned per
-    sequence).  The cu tensors are read on the device only (no synchronisation; a graph replay may change them); a
-    sequence whose entries are not a range of the tensors is skipped, and rows of no sequence keep their contents.
-    workspace: None takes the cached per-(device, stream) scratch; a uint8 tensor on q's device
-    (prefill_varlen_workspace_bytes, 256-byte aligned) is passed as it is.  Returns out [Tq, Hq, D], with return_lse
-    (out, lse [Hq, Tq])."""
+def _prefill_varlen_args(q, k, v, cu_seqlens_q, cu_seqlens_k, causal, softmax_scale, out, return_lse, workspace,
+                         window=None):
+    """The checks and the sfa_prefill_varlen_args of flash_attn_varlen_fwd and flash_attn_varlen_window_fwd (window: the
+    latter's, checked before anything needs a device): (lib, args, out, lse, workspace, device, window as an int)"""
     _require(isinstance(q, torch.Tensor) and q.dtype in _DTYPES,
              f"q must be float16 or bfloat16 (got {getattr(q, 'dtype', type(q))})")
     dt, dev = q.dtype, q.device
@@ -730,6 +723,10 @@ def flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, causal=False, sof
         _require(isinstance(workspace, torch.Tensor) and workspace.dtype == torch.uint8 and workspace.dim() == 1 and
                  workspace.is_contiguous(), "workspace must be a contiguous 1-d uint8 tensor")
         _require(workspace.device == dev, f"workspace must be on {dev}")
+    W = None
+    if window is not None:
+        W = _window_int(window)
+        _require(W >= 1, f"window={window} must be >= 1")
     _require(q.is_cuda, f"q must live on a HIP device (got {dev})")
     lib = _lib.load()
     lse = torch.empty((Hq, Tq), dtype=torch.float32, device=dev) if return_lse else None
@@ -749,9 +746,43 @@ def flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, causal=False, sof
         ws = _workspace(dev, _STATUS_BYTES + need)[_STATUS_BYTES:] if need else None
     else:
         ws = workspace
+    return lib, a, out, lse, ws, dev, W
+
+
+def flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, causal=False, softmax_scale=None, out=None,
+                          return_lse=False, workspace=None):
+    """flash_attn_fwd over packed sequences of different lengths (sfa_prefill_varlen_fwd).  q [Tq, Hq, D], k / v
+    [Tk, Hkv, D] with any token and head strides and D contiguous, fp16 or bf16, D in {64, 128}; cu_seqlens_q /
+    cu_seqlens_k int32 [B + 1] tensors on q's device: sequence b owns the query rows [cu_q[b], cu_q[b+1]) and the key rows
+    [cu_k[b], cu_k[b+1]) and gets what flash_attn_fwd gives for those rows alone (causal: bottom-right aligned per
+    sequence).  The cu tensors are read on the device only (no synchronisation; a graph replay may change them); a
+    sequence whose entries are not a range of the tensors is skipped, and rows of no sequence keep their contents.
+    workspace: None takes the cached per-(device, stream) scratch; a uint8 tensor on q's device
+    (prefill_varlen_workspace_bytes, 256-byte aligned) is passed as it is.  Returns out [Tq, Hq, D], with return_lse
+    (out, lse [Hq, Tq])."""
+    lib, a, out, lse, ws, dev, _ = _prefill_varlen_args(q, k, v, cu_seqlens_q, cu_seqlens_k, causal, softmax_scale, out,
+                                                        return_lse, workspace)
     with torch.cuda.device(dev):
         _lib.check(lib.sfa_prefill_varlen_fwd(ctypes.byref(a), ctypes.c_void_p(ws.data_ptr()) if ws is not None else None,
                                               ws.numel() if ws is not None else 0, _stream_ptr(dev)))
+    return (out, lse) if return_lse else out
+
+
+def flash_attn_varlen_window_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, window, sinks=None, softmax_scale=None, out=None,
+                                 return_lse=False, workspace=None):
+    """flash_attn_varlen_fwd(causal=True) under a sliding window, with an optional attention sink per query head
+    (sfa_prefill_varlen_window_fwd): sequence b gets what flash_attn_window_fwd gives for its rows alone -- row i with
+    causal limit lim = i + (n_k - n_q) sees the keys max(0, lim + 1 - window) .. lim of its own sequence, and its softmax
+    counts one more element with logit sinks[h] (natural-log units, not scaled) and a zero value row.  window: an int
+    >= 1 (>= a sequence's n_k: the causal mask for it); sinks: None or a float32 [Hq] tensor on q's device; every other
+    argument, the workspace included, as in flash_attn_varlen_fwd.  With return_lse the second result is
+    log(exp(sinks[h]) + sum_j exp(s_j)), [Hq, Tq]."""
+    lib, a, out, lse, ws, dev, W = _prefill_varlen_args(q, k, v, cu_seqlens_q, cu_seqlens_k, True, softmax_scale, out,
+                                                        return_lse, workspace, window)
+    with torch.cuda.device(dev):
+        _lib.check(lib.sfa_prefill_varlen_window_fwd(ctypes.byref(a), W, _sinks_ptr(sinks, q.shape[1], dev),
+                                                     ctypes.c_void_p(ws.data_ptr()) if ws is not None else None,
+                                                     ws.numel() if ws is not None else 0, _stream_ptr(dev)))
     return (out, lse) if return_lse else out
 
 
