@@ -33,6 +33,7 @@
  *   sfa_prefill_split_fwd       <- (no reference function: sfa_prefill_fwd with each q-tile's key range split)
  *   sfa_prefill_varlen_fwd      <- (no reference function: sfa_prefill_fwd over packed sequences of different lengths)
  *   sfa_prefill_varlen_window_fwd <- (no reference function: sfa_prefill_varlen_fwd with a sliding window and sinks)
+ *   sfa_prefill_varlen_split_fwd  <- (no reference function: sfa_prefill_varlen_fwd with each q-tile's key range split)
  * The Python-facing mha_fwd_cuda (src/flash_api.cpp:42-68) and the C++ template
  * surface (src/flash_attn.h) in this repo are thin layers over these symbols.
  */
@@ -76,7 +77,9 @@ extern "C" {
  *      sfa_prefill_varlen_fwd (the prefill forward over packed sequences of different lengths) and its sizing function
  *      added under the same version with a struct of their own, sfa_prefill_varlen_args: callers detect them by symbol
  *      sfa_prefill_varlen_window_fwd (the packed prefill forward with a sliding window and attention sinks) added under
- *      the same version beside an unchanged sfa_prefill_varlen_args: callers detect it by symbol */
+ *      the same version beside an unchanged sfa_prefill_varlen_args: callers detect it by symbol
+ *      sfa_prefill_varlen_split_fwd (the packed prefill forward with a split key range), its sizing function and its auto
+ *      rule added under the same version, in the same way */
 #define SFA_ABI_VERSION 4
 
 typedef enum sfa_status {
@@ -683,7 +686,8 @@ int sfa_prefill_window_fwd(const sfa_prefill_args *args, int window, const float
  * Like every entry point it is asynchronous on `stream`, allocates nothing, never synchronises and may be captured in a
  * graph: two launches on the one stream, no parallel branches.
  * Not served: head_dim 256; a window or sinks together with the split (short windows need no split; full attention with
- * sinks is a follow-up); a combine fused into the last-arriving split; a paged or fp8 K/V.
+ * sinks is a follow-up); a combine fused into the last-arriving split; a paged or fp8 K/V.  (Packed sequences of
+ * different lengths: sfa_prefill_varlen_split_fwd, below.)
  */
 int sfa_prefill_split_fwd(const sfa_prefill_args *args, int num_splits, void *workspace, size_t workspace_bytes,
                           void *stream);
@@ -741,8 +745,8 @@ int sfa_prefill_auto_splits(int batch, int heads_q, int seqlen_q, int seqlen_k, 
  * Runs csrc/prefill_varlen_kernel.hip's two kernels; sfa_debug_get("last_prefill_kernel") and "last_prefill_splits" keep
  * their values.  Like every entry point it is asynchronous on `stream`, allocates nothing, never synchronises and may be
  * captured in a graph: two launches on the one stream, no parallel branches.
- * Not served: head_dim 256; a key-range split for batches of few q-tiles; a paged or fp8 K/V; a status word for bad
- * cu_seqlens; backward.  (A sliding window and sinks: sfa_prefill_varlen_window_fwd, below.)
+ * Not served: head_dim 256; a paged or fp8 K/V; a status word for bad cu_seqlens; backward.  (A sliding window and sinks:
+ * sfa_prefill_varlen_window_fwd; a key-range split for batches of few q-tiles: sfa_prefill_varlen_split_fwd, both below.)
  */
 typedef struct sfa_prefill_varlen_args {
     const void *q;
@@ -807,11 +811,78 @@ size_t sfa_prefill_varlen_workspace_bytes(int batch, int total_q);
  * sfa_debug_get("last_prefill_kernel") and "last_prefill_splits" keep their values.  Like every entry point it is
  * asynchronous on `stream`, allocates nothing, never synchronises and may be captured in a graph: two launches on the one
  * stream, no parallel branches.
- * Not served: head_dim 256; two-sided windows; soft-capping; a paged or fp8 K/V; a key-range split for packed batches; a
- * status word for bad cu_seqlens; backward.
+ * Not served: head_dim 256; two-sided windows; soft-capping; a paged or fp8 K/V; a key-range split together with the window
+ * (sfa_prefill_varlen_split_fwd, below, splits the causal and the full mask only); a status word for bad cu_seqlens;
+ * backward.
  */
 int sfa_prefill_varlen_window_fwd(const sfa_prefill_varlen_args *args, int window, const float *sinks, void *workspace,
                                   size_t workspace_bytes, void *stream);
+
+/* ---- packed prefill with a split key range (few q-tiles, long prefixes) ---------------- */
+/*
+ * sfa_prefill_varlen_fwd for packed batches with fewer q-tiles than the chip has compute units -- chunked prefill under
+ * continuous batching: a handful of sequences, each a query block of a few hundred rows against a prefix of thousands of
+ * keys: sfa_prefill_split_fwd's partition on sfa_prefill_varlen_fwd's packed, ragged batches.  Added under ABI version 4
+ * beside an unchanged sfa_prefill_varlen_args: callers detect the three functions by symbol.
+ * Semantics are exactly sfa_prefill_varlen_fwd's: the same o and lse, the same layouts, strides and alignment, cu_seqlens
+ * read on the device only, total_q / total_k, head_dim 64 or 128 (256: SFA_ERR_UNSUPPORTED_HEAD_DIM), fp16 / bf16, GQA,
+ * exact scale, causal of either value, bottom-right aligned per sequence, zeros and lse = -inf for a row without a visible
+ * key (every row of a sequence with n_k == 0), a sequence with n_q == 0 takes no part, an invalid sequence is skipped
+ * with nothing of it read or written, no status word.  Only the work partition differs.  Except:
+ *   max_seqlen_k    a host value, because the lengths live on the device: a partition hint only.  >= 1 (< 1 returns
+ *                   SFA_ERR_BAD_SHAPE).  Results are correct for any value >= 1, whatever the real lengths are.
+ *   num_splits      >= 1: explicit.  <= 0: sfa_prefill_varlen_auto_splits(batch, heads_q, total_q, max_seqlen_k, head_dim,
+ *                   causal), and a workspace that holds fewer splits than that gets the largest count it holds (an empty
+ *                   one: 1), as in sfa_prefill_split_fwd.
+ *   workspace       device scratch of sfa_prefill_varlen_split_workspace_bytes(...) bytes, 256-byte aligned, no status
+ *                   block.  Its contents on entry never matter (NaN, 0x00 and 0xFF give identical results): what is read
+ *                   was written by the same call.
+ * Partition.  nkt_max = ceil(max_seqlen_k / 64).  A request for S splits resolves exactly as in sfa_prefill_split_fwd:
+ * C = ceil(nkt_max / min(S, nkt_max)) tiles per split and S' = ceil(nkt_max / C) splits.  For q-tile qt (256 query rows) of
+ * sequence b, nkt(b, qt) is the number of 64-key tiles its last row sees: ceil(n_k / 64) without a mask; under the causal
+ * mask lim / 64 + 1 with lim = min(256 (qt + 1), n_q) - 1 + n_k - n_q, and 0 when lim < 0.  Split s < S' - 1 owns the tiles
+ * [s C, min((s + 1) C, nkt)); the last split S' - 1 owns [(S' - 1) C, nkt), so a sequence longer than max_seqlen_k is still
+ * computed in full, only unevenly.  A split with s C >= nkt is empty: no workgroup runs for it, nothing of K or V is read
+ * for it, and no partial is written or read.
+ * Workspace layout.  With bound = total_q / 256 + batch q-tile slots, three regions, each rounded up to 256 bytes:
+ *   the q-tile plan of sfa_prefill_varlen_fwd       8 * bound bytes
+ *   the item list, (q-tile slot, split) entries     8 * bound * S' bytes
+ *   the fp32 partials                               bound * heads_q * S' * 256 rows of head_dim + 2 floats
+ * sfa_prefill_varlen_split_workspace_bytes returns exactly this sum; for S' == 1 the plan alone.
+ * What the call promises about memory: everything sfa_prefill_varlen_fwd promises.  A valid sequence's result is a
+ * function of its own rows and of (C, S') only, bit-identical whether it is computed alone or inside any batch; and where
+ * sfa_prefill_split_fwd on the sequence's own [1, heads, n, head_dim] view resolves to the same C and covers the same
+ * tiles per split, the packed call returns that call's bits for the sequence's rows (the same walk, the same ordered
+ * merge).
+ * Argument checks: sfa_prefill_varlen_fwd's, in its order with its texts under this call's name.  Directly after the
+ * alignment step and before the batch == 0 or total_q == 0 return: max_seqlen_k < 1 (SFA_ERR_BAD_SHAPE).  The workspace
+ * checks use the resolved count: NULL (SFA_ERR_NULL_POINTER), not 256-byte aligned (SFA_ERR_BAD_SHAPE), too few bytes for
+ * an explicit num_splits (SFA_ERR_WORKSPACE_TOO_SMALL).  Last, the attention grid of bound * S' * heads_q workgroups or the
+ * combine grid of bound * heads_q * head_dim / 4 that does not fit 2^31 - 1 (SFA_ERR_BAD_SHAPE).
+ * Forwarding: a resolved count of 1 validates under this call's name and then launches exactly what
+ * sfa_prefill_varlen_fwd launches; the output is bit-identical to it, and only the plan part of the workspace is needed.
+ * Every other count runs the plan kernel and csrc/prefill_varlen_split_kernel.hip's three kernels.
+ * sfa_debug_get("last_prefill_splits") reports the resolved count (1: forwarded); "last_prefill_kernel" keeps its value.
+ * Like every entry point it is asynchronous on `stream`, allocates nothing, never synchronises and may be captured in a
+ * graph and replayed with other cu_seqlens contents under the same batch, totals, max_seqlen_k and num_splits: up to four
+ * launches on the one stream, no parallel branches.
+ * Not served: head_dim 256; a window or sinks together with the split; a chunk length per sequence (one C serves the
+ * batch, so one long prefix among short ones is walked by its last split alone); a paged or fp8 K/V; backward.
+ */
+int sfa_prefill_varlen_split_fwd(const sfa_prefill_varlen_args *args, int max_seqlen_k, int num_splits, void *workspace,
+                                 size_t workspace_bytes, void *stream);
+/* Bytes of workspace for `num_splits` (as given to the call: >= 1 explicit, <= 0 the library's choice), with
+ * bound = total_q / 256 + batch and S' the resolved count:
+ *   S' == 1:  up256(8 bound)                                  (= sfa_prefill_varlen_workspace_bytes(batch, total_q))
+ *   S' >= 2:  up256(8 bound) + up256(8 bound S') + 4 (head_dim + 2) * 256 bound heads_q S'
+ * A multiple of 256, the same for a request and the count it resolves to, non-decreasing in num_splits.  Bad dimensions
+ * (a count <= 0, max_seqlen_k < 1, head_dim not 64 / 128): 0. */
+size_t sfa_prefill_varlen_split_workspace_bytes(int batch, int heads_q, int total_q, int max_seqlen_k, int head_dim,
+                                                int num_splits);
+/* The split count the library picks from what the host knows: sfa_prefill_auto_splits' rule and constants (measured on
+ * rectangular problems) for heads_q * ceil(total_q / 256) workgroups and ceil(max_seqlen_k / 64) key tiles, that is
+ * sfa_prefill_auto_splits(1, heads_q, total_q, max_seqlen_k, head_dim, causal).  1 from 256 workgroups on. */
+int sfa_prefill_varlen_auto_splits(int batch, int heads_q, int total_q, int max_seqlen_k, int head_dim, int causal);
 
 /* ---- test / A-B hooks: NOT part of the drop-in surface ------------------------------ */
 /* The launch paths read no environment variable; the test-suite and tools/ select kernel
@@ -824,7 +895,8 @@ int sfa_debug_set(const char *knob, int value);
 /* Read back: the knobs above, and "last_prefill_kernel" = which kernel the last sfa_prefill_fwd of this process
  * launched (the dispatcher's choice included): 1 / 3 the 8-wave 256-row kernel (exact / prescaled), 20 + f the 128-row
  * geometry, 40 + f the 4-wave persistent kernel (f: 1 prescaled, 2 exact), 60 / 61 the head_dim 256 kernels, -1 none
- * yet; "last_prefill_splits" = the resolved split count of this process's last sfa_prefill_split_fwd, 1 if it
+ * yet; "last_prefill_splits" = the resolved split count of this process's last sfa_prefill_split_fwd or
+ * sfa_prefill_varlen_split_fwd, 1 if it
  * forwarded, -1 if there was none yet.  Unknown knob: INT_MIN.  (bench.py names its roofline kernel from this.) */
 int sfa_debug_get(const char *knob);
 

@@ -15,7 +15,7 @@
 //   * biases are honoured (the reference accepts and drops them); an empty tensor means "none";
 //   * the call is asynchronous on the current stream -- no device-wide sync, no per-call malloc;
 //   * num_splits is chosen by the library (the reference hard-codes 4);
-//   * additive entry points: mha_fwd (prefill forward), mha_fwd_split (the same with a split key range), mha_varlen_fwd (the same over packed sequences), compute_rotary_table, check_errors,
+//   * additive entry points: mha_fwd (prefill forward), mha_fwd_split (the same with a split key range), mha_varlen_fwd (the same over packed sequences), mha_varlen_split_fwd (the two together), compute_rotary_table, check_errors,
 //     release_workspaces.
 #include <ATen/hip/HIPContext.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>      // PyTorch-ROCm tensors say "cuda"
@@ -290,11 +290,13 @@ std::vector<at::Tensor> mha_fwd_split(const at::Tensor &q, const at::Tensor &k, 
 // any token and head strides), cu_seqlens_q / cu_seqlens_k int32 [B + 1] on q's device, read there only
 // (include/star_flash_attn.h).  Returns [out] or [out, lse [Hq, Tq]].  The plan lives in the module's per-(device,
 // stream) workspace, behind its 256-byte status block.
-// (windowed: mha_varlen_fwd_window's call, with its window and sinks)
+// (windowed: mha_varlen_fwd_window's call, with its window and sinks; split: mha_varlen_split_fwd's, with its
+// max_seqlen_k and num_splits and the larger workspace)
 static std::vector<at::Tensor> varlen_call(const at::Tensor &q, const at::Tensor &k, const at::Tensor &v,
                                            const at::Tensor &cu_seqlens_q, const at::Tensor &cu_seqlens_k, bool causal,
                                            double softmax_scale, bool return_lse, bool windowed, int64_t window,
-                                           const c10::optional<at::Tensor> &sinks_) {
+                                           const c10::optional<at::Tensor> &sinks_, bool split = false,
+                                           int64_t max_seqlen_k = 0, int64_t num_splits = 0) {
     TORCH_CHECK(q.defined() && q.is_cuda(), "star_flash_attn: q must live on a HIP device");
     const int dt = dtype_code(q, "q");
     for (const at::Tensor *t : {&q, &k, &v}) {
@@ -312,6 +314,10 @@ static std::vector<at::Tensor> varlen_call(const at::Tensor &q, const at::Tensor
                 " entries, cu_seqlens_k ", cu_seqlens_k.size(0));
     TORCH_CHECK(q.size(0) <= INT_MAX && k.size(0) <= INT_MAX && cu_seqlens_q.size(0) <= INT_MAX,
                 "star_flash_attn: too many rows");
+    if (split) {
+        TORCH_CHECK(max_seqlen_k >= 1 && max_seqlen_k <= INT_MAX, "star_flash_attn: max_seqlen_k must be in [1, INT_MAX], got ", max_seqlen_k);
+        TORCH_CHECK(num_splits >= INT_MIN && num_splits <= INT_MAX, "star_flash_attn: num_splits out of range, got ", num_splits);
+    }
     const float *sinks = nullptr;
     if (windowed) {
         TORCH_CHECK(window >= 1 && window <= INT_MAX, "star_flash_attn: window must be in [1, INT_MAX], got ", window);
@@ -342,10 +348,13 @@ static std::vector<at::Tensor> varlen_call(const at::Tensor &q, const at::Tensor
     a.dtype = dt;
     c10::hip::HIPGuardMasqueradingAsCUDA guard(q.device());
     hipStream_t stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(q.device().index()).stream();
-    const size_t need = sfa_prefill_varlen_workspace_bytes(a.batch, a.total_q);
+    const size_t need = split ? sfa_prefill_varlen_split_workspace_bytes(a.batch, a.heads_q, a.total_q, (int)max_seqlen_k,
+                                                                         a.head_dim, (int)num_splits)
+                              : sfa_prefill_varlen_workspace_bytes(a.batch, a.total_q);
     void *ws = nullptr;
     if (need) ws = (char *)workspace(q.device(), stream, 256 + need).data_ptr() + 256;
-    if (windowed) check_status(sfa_prefill_varlen_window_fwd(&a, (int)window, sinks, ws, need, stream), "mha_varlen_fwd_window");
+    if (split) check_status(sfa_prefill_varlen_split_fwd(&a, (int)max_seqlen_k, (int)num_splits, ws, need, stream), "mha_varlen_split_fwd");
+    else if (windowed) check_status(sfa_prefill_varlen_window_fwd(&a, (int)window, sinks, ws, need, stream), "mha_varlen_fwd_window");
     else check_status(sfa_prefill_varlen_fwd(&a, ws, need, stream), "mha_varlen_fwd");
     if (return_lse) return {out, lse};
     return {out};
@@ -365,6 +374,16 @@ std::vector<at::Tensor> mha_varlen_fwd_window(const at::Tensor &q, const at::Ten
                                               int64_t window, c10::optional<at::Tensor> sinks_, double softmax_scale,
                                               bool return_lse) {
     return varlen_call(q, k, v, cu_seqlens_q, cu_seqlens_k, true, softmax_scale, return_lse, true, window, sinks_);
+}
+
+// mha_varlen_fwd with each q-tile's key range cut into num_splits chunks (<= 0: the library's choice) for packed batches of
+// few q-tiles; max_seqlen_k: the host's bound of the longest key range, a partition hint (include/star_flash_attn.h).
+std::vector<at::Tensor> mha_varlen_split_fwd(const at::Tensor &q, const at::Tensor &k, const at::Tensor &v,
+                                             const at::Tensor &cu_seqlens_q, const at::Tensor &cu_seqlens_k,
+                                             int64_t max_seqlen_k, bool causal, int64_t num_splits, double softmax_scale,
+                                             bool return_lse) {
+    return varlen_call(q, k, v, cu_seqlens_q, cu_seqlens_k, causal, softmax_scale, return_lse, false, 0, c10::nullopt, true,
+                       max_seqlen_k, num_splits);
 }
 
 std::vector<at::Tensor> compute_rotary_table(int max_seq_len, int rot_dim, at::ScalarType dtype, at::Device device) {
@@ -411,6 +430,12 @@ PYBIND11_MODULE(star_flash_attn, m) {
           "returns [out] or [out, lse]",
           py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cu_seqlens_q"), py::arg("cu_seqlens_k"), py::arg("window"),
           py::arg("sinks") = py::none(), py::arg("softmax_scale") = 0.0, py::arg("return_lse") = false);
+    m.def("mha_varlen_split_fwd", &mha_varlen_split_fwd,
+          "Attention forward (prefill) over packed sequences with a split key range for batches of few q-tiles: "
+          "returns [out] or [out, lse]",
+          py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cu_seqlens_q"), py::arg("cu_seqlens_k"),
+          py::arg("max_seqlen_k"), py::arg("causal") = false, py::arg("num_splits") = 0, py::arg("softmax_scale") = 0.0,
+          py::arg("return_lse") = false);
     m.def("compute_rotary_table", &compute_rotary_table, "cos/sin LUT [max_seq_len, rot_dim/2]",
           py::arg("max_seq_len"), py::arg("rot_dim"), py::arg("dtype"), py::arg("device"));
 }

@@ -12,6 +12,7 @@ from .ops import (  # noqa: F401
     flash_decode_chunk_kv8_window_sinks, flash_decode_varlen_kv8_window_sinks, flash_attn_fwd,
     flash_attn_window_fwd, flash_attn_split_fwd, prefill_auto_splits, prefill_split_workspace_bytes,
     flash_attn_varlen_fwd, prefill_varlen_workspace_bytes, flash_attn_varlen_window_fwd,
+    flash_attn_varlen_split_fwd, prefill_varlen_auto_splits, prefill_varlen_split_workspace_bytes,
     compute_rotary_table, fill_16bit, check_decode_status, set_sync_checks, release_workspaces,
 )
 from ._lib import SfaError, LIB_PATH, debug_set, debug_get, last_prefill_kernel  # noqa: F401

@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = [
     "sfa_prefill_window_fwd",
     "sfa_prefill_split_fwd", "sfa_prefill_split_workspace_bytes", "sfa_prefill_auto_splits",
     "sfa_prefill_varlen_fwd", "sfa_prefill_varlen_workspace_bytes", "sfa_prefill_varlen_window_fwd",
+    "sfa_prefill_varlen_split_fwd", "sfa_prefill_varlen_split_workspace_bytes", "sfa_prefill_varlen_auto_splits",
 ]
 
 
@@ -158,6 +159,13 @@ def load():
                                                   ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     lib.sfa_prefill_varlen_workspace_bytes.restype = ctypes.c_size_t
     lib.sfa_prefill_varlen_workspace_bytes.argtypes = [ctypes.c_int] * 2
+    lib.sfa_prefill_varlen_split_fwd.restype = ctypes.c_int
+    lib.sfa_prefill_varlen_split_fwd.argtypes = [ctypes.POINTER(PrefillVarlenArgs), ctypes.c_int, ctypes.c_int,
+                                                 ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.sfa_prefill_varlen_split_workspace_bytes.restype = ctypes.c_size_t
+    lib.sfa_prefill_varlen_split_workspace_bytes.argtypes = [ctypes.c_int] * 6
+    lib.sfa_prefill_varlen_auto_splits.restype = ctypes.c_int
+    lib.sfa_prefill_varlen_auto_splits.argtypes = [ctypes.c_int] * 6
     lib.sfa_compute_rotary_table.restype = ctypes.c_int
     lib.sfa_compute_rotary_table.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                              ctypes.c_int, ctypes.c_int, ctypes.c_void_p]

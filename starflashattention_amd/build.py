@@ -35,7 +35,7 @@ KERNEL_SOURCES = ["prefill_w4_kernel.hip", "prefill_w4_kernel_p1.hip", "prefill_
                   "decode_chunk_kv8_window_sinks_kernel.hip", "decode_varlen_kv8_window_sinks_kernel.hip",
                   "decode_window_sinks_kernel.hip", "decode_kv8_window_sinks_kernel.hip", "decode_kernel.hip", "decode_gqa_kernel.hip", "decode_gqa_mfma_kernel.hip", "decode_kv8_kernel.hip", "decode_kv8_window_kernel.hip", "decode_window_kernel.hip",
                   "prefill_d256_kernel.hip",
-                  "prefill_kernel.hip", "prefill_kernel_bm128.hip", "prefill_window_kernel.hip", "prefill_split_kernel.hip", "prefill_varlen_kernel.hip", "prefill_varlen_window_kernel.hip", "prefill_dispatch.hip", "decode_dispatch.hip",
+                  "prefill_kernel.hip", "prefill_kernel_bm128.hip", "prefill_window_kernel.hip", "prefill_split_kernel.hip", "prefill_varlen_kernel.hip", "prefill_varlen_window_kernel.hip", "prefill_varlen_split_kernel.hip", "prefill_dispatch.hip", "decode_dispatch.hip",
                   "aux_kernels.hip", "c_api.hip", "cxx_surface.hip"]
 # The diagnostic builds of the shipping kernels (stamping / event-log builds, prefill_common.h) are never an auto
 # choice of launch_prefill, so the shipping library does not carry them: build_lib(variants=True) compiles the same

@@ -835,14 +835,46 @@ int split_auto(int batch, int heads_q, int seqlen_q, int seqlen_k) {
     return S < 2 ? 1 : split_resolve(nkt, (int)S);
 }
 
-// ---- sfa_prefill_varlen_fwd / sfa_prefill_varlen_window_fwd ----
-struct PrefillVarlenWindow { int window; const float *sinks; };     // what the windowed call adds to the checks
+// ---- sfa_prefill_varlen_split_fwd: the partition, the workspace and the auto rule (include/star_flash_attn.h) ----
+// (64-bit: max_seqlen_k is any int >= 1)
+int varlen_split_key_tiles(int max_seqlen_k) { return (int)(((long long)max_seqlen_k + kSplitTile - 1) / kSplitTile); }
+size_t varlen_plan_bytes(int batch, int total_q) {
+    return align_up(((size_t)total_q / 256 + (size_t)batch) * sizeof(int2), 256);
+}
+// the three regions for `splits` resolved splits (1: the plan alone); saturates, a multiple of 256 all the same
+size_t varlen_split_bytes(int batch, int heads_q, int total_q, int head_dim, int splits) {
+    const size_t plan = varlen_plan_bytes(batch, total_q);
+    if (splits <= 1) return plan;
+    const size_t bound = (size_t)total_q / 256 + (size_t)batch;
+    size_t items, rows, part, sum;
+    if (__builtin_mul_overflow(bound * sizeof(int2), (size_t)splits, &items) ||
+        __builtin_mul_overflow(bound * (size_t)heads_q, (size_t)splits * kSplitRows, &rows) ||
+        __builtin_mul_overflow(rows, (size_t)(head_dim + 2) * sizeof(float), &part) ||      // (a multiple of 256: rows is)
+        __builtin_add_overflow(part, plan + align_up(items, 256), &sum))
+        return ~(size_t)255;
+    return sum;
+}
+// split_auto's rule and constants on what the host knows of a packed batch: heads_q * ceil(total_q / 256) workgroups (the
+// q-tiles of one sequence of total_q rows; the real count is up to batch - 1 larger) and ceil(max_seqlen_k / 64) tiles.
+// The constants were measured on rectangular problems (above); what the packed sweep says about them is in DESIGN 5.24
+// (tools/prefill_varlen_split_bench.py, profiles/prefill_varlen_split_sweep.txt).
+int varlen_split_auto(int batch, int heads_q, int total_q, int max_seqlen_k) {
+    if (batch <= 0) return 1;
+    return split_auto(1, heads_q, total_q, max_seqlen_k < INT_MAX - kSplitTile ? max_seqlen_k : INT_MAX - kSplitTile);
+}
 
-// What the two packed prefill calls check and marshal alike, under the name of the call; w: the windowed call's
-// arguments, checked directly after the alignment step.  Returns a status; *launch is false where there is nothing to do
-// (batch or total_q of 0).
-int prefill_varlen_call(const char *name, const sfa_prefill_varlen_args *a, const PrefillVarlenWindow *w, void *workspace,
-                        size_t workspace_bytes, PrefillVarlenKernelParams *pp, bool *launch) {
+// ---- sfa_prefill_varlen_fwd / sfa_prefill_varlen_window_fwd / sfa_prefill_varlen_split_fwd ----
+struct PrefillVarlenWindow { int window; const float *sinks; };     // what the windowed call adds to the checks
+// what the split call adds: its two arguments; out: the resolved count
+struct PrefillVarlenSplit { int max_seqlen_k, num_splits; int resolved; };
+
+// What the packed prefill calls check and marshal alike, under the name of the call; w: the windowed call's arguments,
+// s: the split call's, checked directly after the alignment step.  With s the workspace checks are those of the resolved
+// count (s->resolved), and the grid check covers the split's two grids.  Returns a status; *launch is false where there is
+// nothing to do (batch or total_q of 0).
+int prefill_varlen_call(const char *name, const sfa_prefill_varlen_args *a, const PrefillVarlenWindow *w,
+                        PrefillVarlenSplit *s, void *workspace, size_t workspace_bytes, PrefillVarlenKernelParams *pp,
+                        bool *launch) {
     *launch = false;
     if (!a) return fail(SFA_ERR_NULL_POINTER, "%s: args is NULL", name);
     if (!a->q || !a->k || !a->v || !a->o || !a->cu_seqlens_q || !a->cu_seqlens_k)
@@ -872,14 +904,33 @@ int prefill_varlen_call(const char *name, const sfa_prefill_varlen_args *a, cons
             return fail(SFA_ERR_BAD_SHAPE, "%s: causal must be non-zero (a two-sided window is not served)", name);
         if (w->window < 1) return fail(SFA_ERR_BAD_SHAPE, "%s: window=%d must be >= 1", name, w->window);
     }
+    if (s && s->max_seqlen_k < 1)
+        return fail(SFA_ERR_BAD_SHAPE, "%s: max_seqlen_k=%d must be >= 1", name, s->max_seqlen_k);
     if (a->batch == 0 || a->total_q == 0) return SFA_OK;
+    int S = 1;      // the resolved split count
+    if (s) {
+        const int nkt = varlen_split_key_tiles(s->max_seqlen_k);
+        if (s->num_splits >= 1) {
+            S = split_resolve(nkt, s->num_splits);
+        } else {
+            // the library's choice, or the largest count the workspace holds (none: 1), as in sfa_prefill_split_fwd
+            S = varlen_split_auto(a->batch, a->heads_q, a->total_q, s->max_seqlen_k);
+            if (workspace || workspace_bytes == 0)
+                while (S > 1 && varlen_split_bytes(a->batch, a->heads_q, a->total_q, a->head_dim, S) > workspace_bytes)
+                    S = split_resolve(nkt, S - 1);
+        }
+        s->resolved = S;
+    }
     if (!workspace) return fail(SFA_ERR_NULL_POINTER, "%s: workspace is NULL", name);
     if ((uintptr_t)workspace & 255) return fail(SFA_ERR_BAD_SHAPE, "%s: workspace must be 256-byte aligned", name);
-    const size_t need = sfa_prefill_varlen_workspace_bytes(a->batch, a->total_q);
+    const size_t need = varlen_split_bytes(a->batch, a->heads_q, a->total_q, a->head_dim, S);
     if (workspace_bytes < need)
         return fail(SFA_ERR_WORKSPACE_TOO_SMALL, "%s: workspace has %zu bytes, need %zu", name, workspace_bytes, need);
     const long long bound = (long long)a->total_q / 256 + a->batch;
-    if (bound * a->heads_q > 0x7fffffffll) return fail(SFA_ERR_BAD_SHAPE, "%s: grid too large", name);
+    // (with splits: an attention workgroup per item slot and head, head_dim / 4 combine blocks per plan slot and head)
+    const long long per_wg = S > 1 ? (S > a->head_dim / 4 ? S : a->head_dim / 4) : 1;
+    if (bound * a->heads_q > 0x7fffffffll || bound * a->heads_q * per_wg > 0x7fffffffll)
+        return fail(SFA_ERR_BAD_SHAPE, "%s: grid too large", name);
 
     PrefillVarlenKernelParams &p = *pp;
     memset(&p, 0, sizeof(p));
@@ -979,13 +1030,13 @@ int sfa_prefill_split_fwd(const sfa_prefill_args *a, int num_splits, void *works
 // has ceil(n_q / 256) <= n_q / 256 + 1 q-tiles, and the n_q / 256 sum to at most total_q / 256).
 size_t sfa_prefill_varlen_workspace_bytes(int batch, int total_q) {
     if (batch <= 0 || total_q <= 0) return 0;
-    return align_up(((size_t)total_q / 256 + (size_t)batch) * sizeof(int2), 256);
+    return varlen_plan_bytes(batch, total_q);
 }
 
 int sfa_prefill_varlen_fwd(const sfa_prefill_varlen_args *a, void *workspace, size_t workspace_bytes, void *stream) {
     PrefillVarlenKernelParams p;
     bool launch;
-    if (const int rc = prefill_varlen_call("sfa_prefill_varlen_fwd", a, nullptr, workspace, workspace_bytes, &p, &launch))
+    if (const int rc = prefill_varlen_call("sfa_prefill_varlen_fwd", a, nullptr, nullptr, workspace, workspace_bytes, &p, &launch))
         return rc;
     if (!launch) return SFA_OK;
     return launch_prefill_varlen(p, a->dtype, a->head_dim, a->causal != 0, (hipStream_t)stream);
@@ -998,7 +1049,7 @@ int sfa_prefill_varlen_window_fwd(const sfa_prefill_varlen_args *a, int window, 
     PrefillVarlenWindowKernelParams wp;
     const PrefillVarlenWindow w{window, sinks};
     bool launch;
-    if (const int rc = prefill_varlen_call("sfa_prefill_varlen_window_fwd", a, &w, workspace, workspace_bytes, &wp.base,
+    if (const int rc = prefill_varlen_call("sfa_prefill_varlen_window_fwd", a, &w, nullptr, workspace, workspace_bytes, &wp.base,
                                            &launch))
         return rc;
     if (!launch) return SFA_OK;
@@ -1007,6 +1058,52 @@ int sfa_prefill_varlen_window_fwd(const sfa_prefill_varlen_args *a, int window, 
     wp.window = window < cap ? window : cap;
     wp.sinks = sinks;
     return launch_prefill_varlen_window(wp, a->dtype, a->head_dim, (hipStream_t)stream);
+}
+
+// ---- sfa_prefill_varlen_split_fwd: the packed call with a split key range (prefill_varlen_split_kernel.hip) ----
+size_t sfa_prefill_varlen_split_workspace_bytes(int batch, int heads_q, int total_q, int max_seqlen_k, int head_dim,
+                                                int num_splits) {
+    if (batch <= 0 || heads_q <= 0 || total_q <= 0 || max_seqlen_k <= 0 || (head_dim != 64 && head_dim != 128)) return 0;
+    const int S = num_splits >= 1 ? split_resolve(varlen_split_key_tiles(max_seqlen_k), num_splits)
+                                  : varlen_split_auto(batch, heads_q, total_q, max_seqlen_k);
+    return varlen_split_bytes(batch, heads_q, total_q, head_dim, S);
+}
+
+int sfa_prefill_varlen_auto_splits(int batch, int heads_q, int total_q, int max_seqlen_k, int head_dim, int causal) {
+    (void)head_dim;
+    (void)causal;
+    return varlen_split_auto(batch, heads_q, total_q, max_seqlen_k);
+}
+
+// sfa_prefill_varlen_fwd with each q-tile's key range cut into splits.  A resolved count of 1: the call is
+// sfa_prefill_varlen_fwd's, launch and all
+int sfa_prefill_varlen_split_fwd(const sfa_prefill_varlen_args *a, int max_seqlen_k, int num_splits, void *workspace,
+                                 size_t workspace_bytes, void *stream) {
+    PrefillVarlenSplitKernelParams sp;
+    PrefillVarlenSplit s{max_seqlen_k, num_splits, 1};
+    bool launch;
+    if (const int rc = prefill_varlen_call("sfa_prefill_varlen_split_fwd", a, nullptr, &s, workspace, workspace_bytes,
+                                           &sp.base, &launch))
+        return rc;
+    if (!launch) return SFA_OK;
+    const int S = s.resolved;
+    const bool causal = a->causal != 0;
+    g_knobs.last_prefill_splits.store(S, std::memory_order_relaxed);
+    if (S == 1) return launch_prefill_varlen(sp.base, a->dtype, a->head_dim, causal, (hipStream_t)stream);
+    // the workspace: the plan, the items, the partials (O, then (m, l)), each from a 256-byte boundary
+    const size_t bound = (size_t)sp.base.bound;
+    char *ws = (char *)workspace + varlen_plan_bytes(a->batch, a->total_q);
+    sp.items = (int2 *)ws;
+    ws += align_up(bound * S * sizeof(int2), 256);
+    const size_t rows = bound * a->heads_q * S * kSplitRows;
+    sp.part_o = (float *)ws;
+    sp.part_ml = (float2 *)(ws + rows * a->head_dim * sizeof(float));
+    sp.num_splits = S;
+    sp.tiles_per_split = split_chunk(varlen_split_key_tiles(max_seqlen_k), S);
+    if (const int rc = launch_prefill_varlen_plan(sp.base, (hipStream_t)stream)) return rc;
+    if (const int rc = launch_prefill_varlen_split_items(sp, causal, (hipStream_t)stream)) return rc;
+    if (const int rc = launch_prefill_varlen_split(sp, a->dtype, a->head_dim, causal, (hipStream_t)stream)) return rc;
+    return launch_prefill_varlen_split_combine(sp, a->dtype, a->head_dim, causal, (hipStream_t)stream);
 }
 
 int sfa_prefill_fwd(const sfa_prefill_args *a, void *stream) {

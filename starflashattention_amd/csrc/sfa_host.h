@@ -229,6 +229,19 @@ struct PrefillVarlenWindowKernelParams {
     const float *sinks;     // [Hq] fp32, one logit per query head (natural-log units, not scaled), or nullptr
 };
 
+// sfa_prefill_varlen_split_fwd (prefill_varlen_split_kernel.hip): the packed prefill forward with each q-tile's key range
+// cut into num_splits chunks of tiles_per_split 64-key tiles, the last chunk open-ended.  The split rides behind the
+// unchanged parameters, as above.  Partials of row r (< 256) of plan slot i, query head h, split s: index
+// ((i * Hq + h) * num_splits + s) * 256 + r of part_ml, times head_dim of part_o.
+struct PrefillVarlenSplitKernelParams {
+    PrefillVarlenKernelParams base;     // every field keeps its meaning
+    int2 *items;            // workspace: [bound * num_splits] (plan slot, split) per attention workgroup slot, (-1, 0) = empty
+    float *part_o;          // workspace: un-normalised fp32 partial outputs
+    float2 *part_ml;        // workspace: (reference max in log2 units, row sum) of each partial
+    int num_splits;         // resolved count, >= 2
+    int tiles_per_split;    // ceil(ceil(max_seqlen_k / 64) / num_splits)
+};
+
 int launch_decode(const DecodeKernelParams &p, int dtype, int head_dim, hipStream_t stream);     // decode_dispatch.hip
 // non-temporal cache loads? (both caches of elem_bytes per element against the Infinity Cache, or the decode_nt knob)
 bool decode_nt(const DecodeKernelParams &p, int head_dim, int elem_bytes);                       // decode_dispatch.hip
@@ -278,7 +291,8 @@ int launch_prefill_window(const PrefillWindowKernelParams &p, int dtype, int hea
 int launch_prefill_split(const PrefillSplitKernelParams &p, int dtype, int head_dim, bool causal, hipStream_t stream);
 int launch_prefill_split_combine(const PrefillSplitKernelParams &p, int dtype, int head_dim, bool causal,
                                  hipStream_t stream);
-// prefill_varlen_kernel.hip: called by sfa_prefill_varlen_fwd, and by sfa_prefill_varlen_window_fwd where it forwards
+// prefill_varlen_kernel.hip: called by sfa_prefill_varlen_fwd, and by sfa_prefill_varlen_window_fwd and
+// sfa_prefill_varlen_split_fwd where they forward
 // (validated dtype, head_dim 64 / 128, B > 0, total_q > 0): the plan kernel, then the attention kernel over the plan, on
 // the same stream
 int launch_prefill_varlen(const PrefillVarlenKernelParams &p, int dtype, int head_dim, bool causal, hipStream_t stream);
@@ -287,6 +301,14 @@ int launch_prefill_varlen_plan(const PrefillVarlenKernelParams &p, hipStream_t s
 // prefill_varlen_window_kernel.hip: called by sfa_prefill_varlen_window_fwd only (validated as above, window >= 1): the
 // plan kernel, then the windowed attention kernel over the plan, on the same stream
 int launch_prefill_varlen_window(const PrefillVarlenWindowKernelParams &p, int dtype, int head_dim, hipStream_t stream);
+// prefill_varlen_split_kernel.hip: called by sfa_prefill_varlen_split_fwd only (validated as above, two or more splits):
+// the item list from the plan (launch_prefill_varlen_plan comes first), the attention kernel over the items, then the
+// combine, on the same stream
+int launch_prefill_varlen_split_items(const PrefillVarlenSplitKernelParams &p, bool causal, hipStream_t stream);
+int launch_prefill_varlen_split(const PrefillVarlenSplitKernelParams &p, int dtype, int head_dim, bool causal,
+                                hipStream_t stream);
+int launch_prefill_varlen_split_combine(const PrefillVarlenSplitKernelParams &p, int dtype, int head_dim, bool causal,
+                                        hipStream_t stream);
 int launch_rotary_table(void *cos_t, void *sin_t, int max_seq_len, int rot_dim, int dtype, hipStream_t stream);
 int launch_fill16(void *arr, uint16_t bits, size_t n, hipStream_t stream);
 
@@ -301,7 +323,7 @@ struct DebugKnobs {
     std::atomic<int> decode_gqa_mfma{-1};   // decode_dispatch.hip: 0 forces the VALU grouped-query kernel
     std::atomic<int> bm128_one_wg{-1};      // prefill_kernel_bm128.hip: 1 = one workgroup per CU (A/B library only)
     std::atomic<int> last_prefill_kernel{-1};   // written by launch_prefill: what ran last (sfa_debug_get)
-    std::atomic<int> last_prefill_splits{-1};   // written by sfa_prefill_split_fwd: the resolved split count (1: forwarded)
+    std::atomic<int> last_prefill_splits{-1};   // written by sfa_prefill_split_fwd / sfa_prefill_varlen_split_fwd: the resolved split count (1: forwarded)
 };
 extern DebugKnobs g_knobs;
 

@@ -786,6 +786,46 @@ def flash_attn_varlen_window_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, window, si
     return (out, lse) if return_lse else out
 
 
+def prefill_varlen_auto_splits(batch, heads_q, total_q, max_seqlen_k, head_dim, causal=False):
+    """sfa_prefill_varlen_auto_splits: the split count flash_attn_varlen_split_fwd(num_splits=0) picks for these shapes."""
+    return _lib.load().sfa_prefill_varlen_auto_splits(int(batch), int(heads_q), int(total_q), int(max_seqlen_k),
+                                                      int(head_dim), 1 if causal else 0)
+
+
+def prefill_varlen_split_workspace_bytes(batch, heads_q, total_q, max_seqlen_k, head_dim, num_splits=0):
+    """sfa_prefill_varlen_split_workspace_bytes: bytes of workspace flash_attn_varlen_split_fwd needs for num_splits
+    (0: auto): the plan, the item list and the fp32 partials."""
+    return _lib.load().sfa_prefill_varlen_split_workspace_bytes(int(batch), int(heads_q), int(total_q), int(max_seqlen_k),
+                                                                int(head_dim), int(num_splits))
+
+
+def flash_attn_varlen_split_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_k, causal=False, num_splits=0,
+                                softmax_scale=None, out=None, return_lse=False, workspace=None):
+    """flash_attn_varlen_fwd with each q-tile's key range cut into num_splits chunks, one workgroup each, and a combine
+    over the fp32 partials (sfa_prefill_varlen_split_fwd): for packed batches with fewer 256-row q-tiles than compute
+    units -- a few query blocks against long prefixes.  Same o and lse as flash_attn_varlen_fwd.  max_seqlen_k: an int
+    >= 1, the host's bound of the longest key range; a partition hint only (a longer sequence is still computed in full).
+    num_splits <= 0: the library's choice (prefill_varlen_auto_splits); a count that resolves to 1 is
+    flash_attn_varlen_fwd's launch, bit for bit.  workspace: None takes the cached per-(device, stream) scratch; a uint8
+    tensor on q's device (prefill_varlen_split_workspace_bytes, 256-byte aligned) is passed as it is."""
+    _require(isinstance(max_seqlen_k, int) and not isinstance(max_seqlen_k, bool),
+             f"max_seqlen_k={max_seqlen_k!r} must be an int")
+    _require(max_seqlen_k >= 1, f"max_seqlen_k={max_seqlen_k} must be >= 1")
+    _require(isinstance(num_splits, int) and not isinstance(num_splits, bool), f"num_splits={num_splits!r} must be an int")
+    lib, a, out, lse, ws, dev, _ = _prefill_varlen_args(q, k, v, cu_seqlens_q, cu_seqlens_k, causal, softmax_scale, out,
+                                                        return_lse, workspace)
+    if workspace is None:
+        need = lib.sfa_prefill_varlen_split_workspace_bytes(a.batch, a.heads_q, a.total_q, max_seqlen_k, a.head_dim,
+                                                            num_splits)
+        # behind the 256-byte status block of the decode calls, whose sticky word this call must not overwrite
+        ws = _workspace(dev, _STATUS_BYTES + need)[_STATUS_BYTES:] if need else None
+    with torch.cuda.device(dev):
+        _lib.check(lib.sfa_prefill_varlen_split_fwd(ctypes.byref(a), max_seqlen_k, num_splits,
+                                                    ctypes.c_void_p(ws.data_ptr()) if ws is not None else None,
+                                                    ws.numel() if ws is not None else 0, _stream_ptr(dev)))
+    return (out, lse) if return_lse else out
+
+
 def compute_rotary_table(max_seq_len, rot_dim, dtype=torch.float16, device="cuda"):
     lib = _lib.load()
     device = torch.device(device)
