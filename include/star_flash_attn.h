@@ -573,8 +573,18 @@ int sfa_decode_varlen_kv8_window_sinks(const sfa_decode_args *args, const float 
 /* ---- prefill: O = softmax(mask(Q K^T * scale)) V ------------------------------- */
 /*
  * q [batch, heads_q, seqlen_q, head_dim], k/v [batch, heads_kv, seqlen_k, head_dim],
- * o like q; any batch/head/seq strides (in elements), head_dim contiguous, 16-byte
- * aligned rows.  heads_q % heads_kv == 0 (GQA: query head h reads kv head
+ * o like q; batch/head/seq strides in elements, >= 0 and multiples of 8, head_dim
+ * contiguous, 16-byte aligned rows.  Batch and head strides and the seq strides of q
+ * and o are unbounded (64-bit).  The seq stride of k and of v is bounded at head_dim 64
+ * and 128, where the kernels address a key row inside its tile in 32 bits: at most
+ * floor((2^32 - 1 - 16 * (head_dim / 8 - 1)) / (2 * (T - 1)) / 8) * 8 elements for a tile
+ * of T keys -- 34087040 for the 64-key tiles of sfa_prefill_window_fwd and
+ * sfa_prefill_split_fwd and of this call's 256-row kernel, 69273656 (head_dim 64:
+ * 69273664) for the 32-key tiles of its 128-row kernel (whichever the call picks) -- and what the 4-wave kernel's
+ * descriptors cover, from which the call falls back to the former.  The packed calls
+ * below bound the token stride of k and v by the same 34087040.  A stride above the
+ * limit returns SFA_ERR_BAD_SHAPE ("... k seq stride N exceeds LIMIT elements ...");
+ * head_dim 256 is served at any stride.  heads_q % heads_kv == 0 (GQA: query head h reads kv head
  * h / (heads_q/heads_kv)).  causal != 0: key j visible to query i iff
  * j <= i + (seqlen_k - seqlen_q).  lse (optional, fp32 [batch, heads_q, seqlen_q],
  * contiguous) receives log(sum(exp(scaled scores))) per row.  A row with no visible
@@ -709,7 +719,9 @@ int sfa_prefill_auto_splits(int batch, int heads_q, int seqlen_q, int seqlen_k, 
  * sequences one after another, delimited by cu_seqlens_q / cu_seqlens_k.  Added under ABI version 4 with a struct of its
  * own, beside an unchanged sfa_prefill_args: callers detect the two functions by symbol.
  *   q               [total_q, heads_q, head_dim]; k, v [total_k, heads_kv, head_dim]; o like q.  {token, head} strides in
- *                   elements, >= 0 and multiples of 8, head_dim contiguous, 16-byte aligned.
+ *                   elements, >= 0 and multiples of 8, head_dim contiguous, 16-byte aligned.  The token stride of k and of v
+ *                   is at most 34087040 elements (sfa_prefill_args above: the 64-key tiles' 32-bit row offset); a larger
+ *                   one returns SFA_ERR_BAD_SHAPE ("... k token stride N exceeds 34087040 elements ...") with the strides.
  *   lse             optional, fp32 [heads_q, total_q], contiguous, 4-byte aligned: the row of packed query row r of head h
  *                   is h * total_q + r.
  *   cu_seqlens_q, cu_seqlens_k   device int32 [batch + 1], 4-byte aligned.  Sequence b owns the packed query rows

@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstring>
 
+#include "prefill_common.h"
 #include "sfa_host.h"
 
 namespace sfa {
@@ -732,8 +733,10 @@ int sfa_kv8_quantize(void *dst, const void *src, const float *scale, int64_t row
 
 namespace {
 
-// What sfa_prefill_fwd, sfa_prefill_window_fwd and sfa_prefill_split_fwd check and marshal alike, under the name of the call.  d256: head_dim
-// 256 is served.  Returns a status; *launch is false where there is nothing to do (batch or seqlen_q of 0).  p->nq_tiles
+// What sfa_prefill_fwd, sfa_prefill_window_fwd and sfa_prefill_split_fwd check and marshal alike, under the name of the call.  d256:
+// sfa_prefill_fwd itself -- head_dim 256 is served, and the K / V seq stride is checked by launch_prefill against the kernel
+// it picks; the other two run prefill_stream.h's 64-key tiles (or forward to kernels with the same limit or a wider one)
+// and check it here.  Returns a status; *launch is false where there is nothing to do (batch or seqlen_q of 0).  p->nq_tiles
 // and p->bh_per_xcd are set for seqlen_k > 0.
 int prefill_call(const char *name, const sfa_prefill_args *a, bool d256, PrefillKernelParams *pp, bool *launch) {
     *launch = false;
@@ -754,6 +757,9 @@ int prefill_call(const char *name, const sfa_prefill_args *a, bool d256, Prefill
         for (int i = 0; i < 3; ++i)
             if (st[t][i] < 0 || (st[t][i] % 8) != 0)
                 return fail(SFA_ERR_BAD_SHAPE, "%s: strides must be >= 0 and multiples of 8 elements", name);
+    if (!d256)
+        if (const int rc = check_prefill_kv_pitch(name, "seq", a->k_stride[2], a->v_stride[2], prefill::kBN, a->head_dim))
+            return rc;
     if (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->o) & 15)
         return fail(SFA_ERR_BAD_SHAPE, "%s: tensors must be 16-byte aligned", name);
     if ((long long)a->batch * a->heads_q > (1ll << 24))
@@ -894,6 +900,9 @@ int prefill_varlen_call(const char *name, const sfa_prefill_varlen_args *a, cons
         for (int i = 0; i < 2; ++i)
             if (st[t][i] < 0 || (st[t][i] % 8) != 0)
                 return fail(SFA_ERR_BAD_SHAPE, "%s: strides must be >= 0 and multiples of 8 elements", name);
+    // (the packed kernels all walk prefill_stream.h's 64-key tiles)
+    if (const int rc = check_prefill_kv_pitch(name, "token", a->k_stride[0], a->v_stride[0], prefill::kBN, a->head_dim))
+        return rc;
     if (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->o) & 15)
         return fail(SFA_ERR_BAD_SHAPE, "%s: tensors must be 16-byte aligned", name);
     if (((uintptr_t)a->cu_seqlens_q | (uintptr_t)a->cu_seqlens_k | (uintptr_t)a->lse) & 3)

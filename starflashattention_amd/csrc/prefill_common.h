@@ -54,6 +54,26 @@ int launch_prefill_w4(const PrefillKernelParams &p, int dtype, int head_dim, boo
                       int force = 0);
 // whether one head's Q / K / V rows fit the 32-bit buffer descriptors of the 4-wave kernel (else: the 8-wave kernel)
 bool prefill_w4_serves(const PrefillKernelParams &p, int head_dim);
+// The K / V row pitch (elements between two keys: the seq stride, the token stride of a packed call) the 8-wave kernels
+// address.  They keep a tile's base in 64 bits and form a row's byte offset inside the tile in 32: row * 2 * pitch +
+// 16 * chunk, row < tile_rows, chunk < head_dim / 8 (prefill_stream.h and prefill_kernel.hip: tiles of prefill::kBN
+// keys; prefill_kernel_bm128.hip: of kBm128Keys).  The limit is the largest multiple of 8 at which the last chunk of a
+// tile's last row stays below 2^32; the entry points reject what lies above it, the hot loops stay as they are.
+// prefill_d256_kernel.hip indexes in 64 bits and has no such limit; the 4-wave kernels guard their descriptors
+// (prefill_w4_serves, prefill_w4d_serves).
+constexpr int kBm128Keys = 32;
+constexpr long long prefill_max_kv_pitch(int tile_rows, int head_dim) {
+    return ((1ll << 32) - 1 - 16 * (head_dim / 8 - 1)) / (2 * (tile_rows - 1)) / 8 * 8;
+}
+// SFA_OK, or SFA_ERR_BAD_SHAPE under the call's name `name`; what: "seq" or "token"
+inline int check_prefill_kv_pitch(const char *name, const char *what, long long k_pitch, long long v_pitch, int tile_rows,
+                                  int head_dim) {
+    const long long limit = prefill_max_kv_pitch(tile_rows, head_dim);
+    if (k_pitch <= limit && v_pitch <= limit) return SFA_OK;
+    return fail(SFA_ERR_BAD_SHAPE, "%s: %s %s stride %lld exceeds %lld elements, the row pitch the %d-key tiles address at "
+                "head_dim %d", name, k_pitch > limit ? "k" : "v", what, k_pitch > limit ? k_pitch : v_pitch, limit,
+                tile_rows, head_dim);
+}
 // the flavours of the 4-wave kernel that live in translation units of their own (prefill_w4_kernel_p1..3.hip; bf16 exact
 // scale is in prefill_w4_kernel.hip itself): called by launch_prefill_w4 only
 int launch_prefill_w4_fp16_exact(const PrefillKernelParams &p, bool causal, hipStream_t stream);

@@ -78,10 +78,28 @@ int auto_prefill_impl(const PrefillKernelParams &p, int head_dim, bool causal) {
     return wgs < (causal ? 128 : 192) ? kPrefillBm128 : kPrefill8w;
 }
 
+// Keys per tile of the kernel `which` names where that kernel forms a key row's offset in 32 bits (prefill_common.h's
+// pitch limit), 0 where it does not: the 4-wave kernels check their own descriptors, an unknown id fails on its own.
+int pitch_bound_tile(int which) {
+    switch (which) {
+        case kPrefill8w: case kPrefill8wPrescaled: case kPrefill8wExact: case kPrefill8wUnstaged: case kPrefill8wStamps:
+            return prefill::kBN;
+        case kPrefillBm128: case kPrefillBm128Prescaled: case kPrefillBm128Exact:
+            return kBm128Keys;
+        default:
+            return 0;
+    }
+}
+
 }  // namespace
 
 int launch_prefill(const PrefillKernelParams &p, int dtype, int head_dim, bool causal, hipStream_t stream) {
     int which = g_knobs.prefill_impl.load(std::memory_order_relaxed);
+    // The K / V row pitch against the kernel that would run: a check of the call's arguments, so it comes before those
+    // of the debug knob.  (head_dim 256 has prefill_d256_kernel.hip, which indexes in 64 bits, behind the 4-wave kernel.)
+    if (head_dim != 256)
+        if (const int tile = pitch_bound_tile(which == kPrefillAuto ? auto_prefill_impl(p, head_dim, causal) : which))
+            if (const int rc = check_prefill_kv_pitch("sfa_prefill_fwd", "seq", p.ks[2], p.vs[2], tile, head_dim)) return rc;
     if (const int rc = check_prefill_impl(which, p)) return rc;
     auto ran = [](int id) { g_knobs.last_prefill_kernel.store(id, std::memory_order_relaxed); };
     const int flavour = p.fast_scale ? 1 : 2;       // what "by policy" resolves to (1 prescaled, 2 exact)

@@ -27,7 +27,7 @@ namespace {
 
 using namespace prefill;
 
-constexpr int kBM2 = 128, kBN2 = 32, kThreads2 = 256;
+constexpr int kBM2 = 128, kBN2 = kBm128Keys, kThreads2 = 256;     // (the key tile bounds the K/V pitch: prefill_common.h)
 
 template <class Tr, int D, bool CAUSAL, int PF, int ORD>
 __global__ void __launch_bounds__(kThreads2, 2)

@@ -613,8 +613,9 @@ def _prefill_args(q, k, v, out, return_lse, softmax_scale):
 
 
 def flash_attn_fwd(q, k, v, causal=False, softmax_scale=None, out=None, return_lse=False, fast_scale=False):
-    """O = softmax(mask(Q K^T * scale)) V.   q [B,Hq,Sq,D], k/v [B,Hkv,Sk,D] (any batch/head/seq
-    strides, D contiguous), fp16 or bf16, D in {64,128,256}.  causal is bottom-right aligned.
+    """O = softmax(mask(Q K^T * scale)) V.   q [B,Hq,Sq,D], k/v [B,Hkv,Sk,D] (batch/head/seq strides that are
+    multiples of 8, D contiguous; at D 64 / 128 the seq stride of k and v is bounded, about 34 M elements -- the
+    limits are in include/star_flash_attn.h), fp16 or bf16, D in {64,128,256}.  causal is bottom-right aligned.
     fast_scale=True (ignored with return_lse) allows the prescaled-Q kernels: ~5 % faster, the scale is
     folded into Q in 16 bit, so the score error grows with the logits (include/star_flash_attn.h)."""
     lib = _lib.load()
@@ -752,7 +753,8 @@ def _prefill_varlen_args(q, k, v, cu_seqlens_q, cu_seqlens_k, causal, softmax_sc
 def flash_attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, causal=False, softmax_scale=None, out=None,
                           return_lse=False, workspace=None):
     """flash_attn_fwd over packed sequences of different lengths (sfa_prefill_varlen_fwd).  q [Tq, Hq, D], k / v
-    [Tk, Hkv, D] with any token and head strides and D contiguous, fp16 or bf16, D in {64, 128}; cu_seqlens_q /
+    [Tk, Hkv, D] with token and head strides that are multiples of 8 (k and v: a token stride of at most 34087040
+    elements) and D contiguous, fp16 or bf16, D in {64, 128}; cu_seqlens_q /
     cu_seqlens_k int32 [B + 1] tensors on q's device: sequence b owns the query rows [cu_q[b], cu_q[b+1]) and the key rows
     [cu_k[b], cu_k[b+1]) and gets what flash_attn_fwd gives for those rows alone (causal: bottom-right aligned per
     sequence).  The cu tensors are read on the device only (no synchronisation; a graph replay may change them); a
