@@ -1,5 +1,6 @@
 """CPU reference of the multi-token decode step over an fp8 (e4m3) KV cache (sfa_decode_chunk_kv8, sfa_decode_varlen_kv8)
-and the helpers the two GPU test files share.
+and the helpers the two GPU test files share.  The arithmetic is that of tests/serving_model.py; the functions here are
+adapters over it.
 
 The contract is "what n successive sfa_decode_kv8 calls give".  chunk_kv8_ref states it the way the header does -- append
 the quantised rows of all new tokens, then let token t attend to the rows [0, pos + t] of the cache AFTER the append --
@@ -12,34 +13,43 @@ reference quantiser, the output against the cache after the call."""
 import numpy as np
 
 import kv8_ref
-from oracle import rope_interleaved, round_to
+import serving_model as sm
+from oracle import round_to
+from window_ref import TOL  # noqa: F401  (the project's decode tolerances, atol = rtol)
 
-TOL = {"fp16": 2e-3, "bf16": 1.6e-2}            # the project's decode tolerances (tests/test_decode_gpu.py), atol = rtol
 L, M, LAYER = 2, 256, 1
 
 
+def attend_bytes(q16, k8, v8, pos, window, sinks, k_scale, v_scale, scale):
+    """The model's attention over a given byte cache, for attend(), chunk_kv8_window_ref.attend and
+    kv8_sinks_ref.attend_sinks: q16 [n, H, D] float64 rotated, rounded queries of the tokens at pos .. pos + n - 1 of one
+    sequence; k8 / v8 [M, Hkv, D] uint8, one (sequence, layer) of the cache after the append.  Returns (o [n, H, D], lse
+    [n, H] without the sink), float64."""
+    call = sm.make_call(None, q16.shape[1], [pos], [len(q16)], None, 0, window=window, sinks=sinks, k_scale=k_scale,
+                        v_scale=v_scale, softmax_scale=scale)
+    return sm.attend_rows(q16, k8, v8, int(pos), call, with_lse=True)
+
+
 def attend(q16, k8, v8, pos, k_scale=None, v_scale=None, scale=None):
-    """q16 [n, H, D] float64 rotated, rounded queries of the tokens at pos .. pos + n - 1 of one sequence; k8 / v8
-    [M, Hkv, D] uint8, one (sequence, layer) of the cache after the append.  Token t attends to the rows [0, pos + t].
-    Returns o [n, H, D] float64.  (The expressions are kv8_ref.decode_kv8_ref's, so that the two agree to the bit.)"""
-    n, H, D = q16.shape
-    Hkv = k8.shape[1]
-    G = H // Hkv
-    if scale is None:
-        scale = 1.0 / np.sqrt(float(D))
-    ks = np.ones(Hkv, np.float32) if k_scale is None else np.asarray(k_scale, dtype=np.float32)
-    vs = np.ones(Hkv, np.float32) if v_scale is None else np.asarray(v_scale, dtype=np.float32)
-    o = np.zeros((n, H, D), dtype=np.float64)
-    for t in range(n):
-        K = kv8_ref.dequantize(k8[:pos + t + 1], ks)
-        V = kv8_ref.dequantize(v8[:pos + t + 1], vs)
-        K, V = np.repeat(K, G, axis=1), np.repeat(V, G, axis=1)
-        sc = np.einsum("hd,thd->ht", q16[t], K) * scale
-        sc -= sc.max(axis=1, keepdims=True)
-        p = np.exp(sc)
-        p /= p.sum(axis=1, keepdims=True)
-        o[t] = np.einsum("ht,thd->hd", p, V)
-    return o
+    """attend_bytes without a window or sinks: token t attends to the rows [0, pos + t].  Returns o [n, H, D] float64."""
+    return attend_bytes(q16, k8, v8, pos, None, None, k_scale, v_scale, scale)[0]
+
+
+def chunk_kv8_model(tokens, k8, v8, seq_len, idx_layer, rot_dim, dtype, window, sinks, k_scale, v_scale, q_bias, k_bias, v_bias,
+                    cos_table, sin_table, scale):
+    """The multi-token call over an fp8 cache through the model, for chunk_kv8_ref and chunk_kv8_window_ref.
+    chunk_kv8_window_ref (window, sinks: None here).  k8 / v8 are MUTATED.  Returns dict(o, q16, lse = per sequence float64)."""
+    tokens = [np.asarray(t) for t in tokens]
+    Mx = k8.shape[2]
+    pos = [int(p) if len(t) else 0 for p, t in zip(seq_len, tokens)]        # (a sequence without tokens may say anything)
+    for b, (p, t) in enumerate(zip(pos, tokens)):
+        if not (0 <= p and p + len(t) <= Mx):
+            raise ValueError(f"sequence {b}: rows [{p}, {p + len(t)}) outside [0, memory_max_len={Mx})")
+    call = sm.make_call(dtype, tokens[0].shape[1] - 2 * k8.shape[3], pos, [len(t) for t in tokens], tokens, idx_layer, rot_dim,
+                        q_bias=q_bias, k_bias=k_bias, v_bias=v_bias, cos=cos_table, sin=sin_table, window=window, sinks=sinks,
+                        k_scale=k_scale, v_scale=v_scale, softmax_scale=scale)
+    app, res = sm.run((k8, v8), call, in_place=True)
+    return dict(o=[r[0] for r in res], q16=app["q16"], lse=[r[1] for r in res])
 
 
 def chunk_kv8_ref(tokens, k8, v8, seq_len, idx_layer, rot_dim, dtype, k_scale=None, v_scale=None, q_bias=None,
@@ -47,38 +57,9 @@ def chunk_kv8_ref(tokens, k8, v8, seq_len, idx_layer, rot_dim, dtype, k_scale=No
     """tokens: one [n_b, H + 2*Hkv, D] float array per sequence (n_b may be 0; values representable in `dtype`).
     k8, v8 [B, L, M, Hkv, D] uint8, MUTATED at [b, idx_layer, seq_len[b] .. seq_len[b] + n_b).
     Returns dict(o = per sequence [n_b, H, D] float64, q16 = per sequence [n_b, H, D] float64)."""
-    Hkv = k8.shape[3]
-    Mx = k8.shape[2]
-    out_o, out_q = [], []
-    for b, tok in enumerate(tokens):
-        tok = np.asarray(tok)
-        n, HH, D = tok.shape
-        H = HH - 2 * Hkv
-        pos = int(seq_len[b])
-        if n and not (0 <= pos and pos + n <= Mx):
-            raise ValueError(f"sequence {b}: rows [{pos}, {pos + n}) outside [0, memory_max_len={Mx})")
-        q16 = np.zeros((n, H, D), dtype=np.float64)
-        for t in range(n):
-            q = tok[t, :H].astype(np.float64)
-            k = tok[t, H:H + Hkv].astype(np.float64)
-            v = tok[t, H + Hkv:].astype(np.float64)
-            if q_bias is not None:
-                q = q + np.asarray(q_bias, dtype=np.float64)
-            if k_bias is not None:
-                k = k + np.asarray(k_bias, dtype=np.float64)
-            if v_bias is not None:
-                v = v + np.asarray(v_bias, dtype=np.float64)
-            c = s = None
-            if cos_table is not None and rot_dim > 0:
-                c, s = cos_table[pos + t], sin_table[pos + t]
-            q16[t] = round_to(rope_interleaved(q, pos + t, rot_dim, cos=c, sin=s), dtype).astype(np.float64)
-            k16 = round_to(rope_interleaved(k, pos + t, rot_dim, cos=c, sin=s), dtype)
-            v16 = round_to(v, dtype)
-            k8[b, idx_layer, pos + t] = kv8_ref.quantize(k16, k_scale)
-            v8[b, idx_layer, pos + t] = kv8_ref.quantize(v16, v_scale)
-        out_q.append(q16)
-        out_o.append(attend(q16, k8[b, idx_layer], v8[b, idx_layer], pos, k_scale, v_scale, scale))
-    return dict(o=out_o, q16=out_q)
+    ref = chunk_kv8_model(tokens, k8, v8, seq_len, idx_layer, rot_dim, dtype, None, None, k_scale, v_scale, q_bias, k_bias, v_bias,
+                          cos_table, sin_table, scale)
+    return dict(o=ref["o"], q16=ref["q16"])
 
 
 # ---- what the GPU tests share ------------------------------------------------------------------------------------------

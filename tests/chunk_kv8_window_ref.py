@@ -1,11 +1,11 @@
-"""fp64 reference, problems and device harness of sfa_decode_chunk_kv8_window / sfa_decode_varlen_kv8_window (the sliding
+"""Reference, problems and device harness of sfa_decode_chunk_kv8_window / sfa_decode_varlen_kv8_window (the sliding
 window in the multi-token decode calls over an fp8 e4m3 KV cache) for tests/test_decode_chunk_kv8_window_{cpu,gpu}.py and
 tests/test_decode_varlen_kv8_window_gpu.py.
 
-The reference is chunk_kv8_ref.chunk_kv8_ref -- the prologue of every token and the append of its quantised rows -- plus
-attend() with a lower bound: token t attends to the rows [lo_t, pos + t] of the cache AFTER the append, lo_t = max(0, pos
-+ t + 1 - window).  Rows below lo_0 never enter a windowed result, so they may hold the NaN byte 0x7F.  With window None,
-or any window >= pos + n, attend() evaluates chunk_kv8_ref.attend's expressions on the same slices: the same bits.
+The reference is chunk_kv8_ref.chunk_kv8_ref -- the prologue of every token and the append of its quantised rows -- with a
+lower bound, through the same adapter over tests/serving_model.py: token t attends to the rows [lo_t, pos + t] of the
+cache AFTER the append, lo_t = max(0, pos + t + 1 - window).  Rows below lo_0 never enter a windowed result, so they may
+hold the NaN byte 0x7F.  With window None, or any window >= pos + n, the bits are chunk_kv8_ref's.
 
 How the device is checked is how tests/test_decode_chunk_kv8_gpu.py checks it: (a) the appended bytes against the
 reference quantiser (chunk_kv8_ref.check_bytes: V exact, K within one e4m3 step and > 98 % identical per call, every
@@ -31,6 +31,7 @@ from window_ref import TOL, window_lo  # noqa: F401
 B, HKV, L, M, LAYER, SPARE = 4, 2, 2, 1408, 1, 3
 LENS = (0, 5, 130, 1000)
 QTILE, KTILE = 256, 64
+assert (HKV, L, M, SPARE) == (cw.HKV, cw.L, cw.M, cw.SPARE)     # to_layout / from_layout below are chunk_window_ref's
 FILL = 0x33                                     # what the pages no sequence owns hold
 
 
@@ -41,39 +42,18 @@ def attend(q16, k8, v8, pos, window, k_scale=None, v_scale=None, scale=None):
     pos .. pos + n - 1 of one sequence; k8 / v8 [M, Hkv, D] uint8, one (sequence, layer) of the cache after the append.
     Token t attends to the rows [max(0, pos + t + 1 - window), pos + t] (window None: from row 0).  Returns o [n, H, D]
     float64."""
-    n, H, D = q16.shape
-    Hkv = k8.shape[1]
-    G = H // Hkv
-    if scale is None:
-        scale = 1.0 / np.sqrt(float(D))
-    ks = np.ones(Hkv, np.float32) if k_scale is None else np.asarray(k_scale, dtype=np.float32)
-    vs = np.ones(Hkv, np.float32) if v_scale is None else np.asarray(v_scale, dtype=np.float32)
-    o = np.zeros((n, H, D), dtype=np.float64)
-    for t in range(n):
-        lo = window_lo(pos + t, window)
-        K = kv8_ref.dequantize(k8[lo:pos + t + 1], ks)
-        V = kv8_ref.dequantize(v8[lo:pos + t + 1], vs)
-        K, V = np.repeat(K, G, axis=1), np.repeat(V, G, axis=1)
-        sc = np.einsum("hd,thd->ht", q16[t], K) * scale
-        sc -= sc.max(axis=1, keepdims=True)
-        p = np.exp(sc)
-        p /= p.sum(axis=1, keepdims=True)
-        o[t] = np.einsum("ht,thd->hd", p, V)
-    return o
+    return ckr.attend_bytes(q16, k8, v8, pos, window, None, k_scale, v_scale, scale)[0]
 
 
 def chunk_kv8_window_ref(tokens, k8, v8, seq_len, idx_layer, rot_dim, dtype, window, k_scale=None, v_scale=None,
                          scale=None, **kw):
     """chunk_kv8_ref.chunk_kv8_ref's arguments and result, plus `window` (None = no window).  k8 / v8 are MUTATED at the
-    appended rows.  The prologue and the append are chunk_kv8_ref's own; its full-history outputs (NaN where a row below
-    the window holds 0x7F) are replaced by the windowed ones."""
-    with np.errstate(invalid="ignore"):
-        ref = ckr.chunk_kv8_ref(tokens, k8, v8, seq_len, idx_layer, rot_dim, dtype, k_scale, v_scale, scale=scale, **kw)
-    if window is None:
-        return ref
-    o = [attend(q16, k8[b, idx_layer], v8[b, idx_layer], int(seq_len[b]), window, k_scale, v_scale, scale)
-         for b, q16 in enumerate(ref["q16"])]
-    return dict(o=o, q16=ref["q16"])
+    appended rows."""
+    bias_and_tables = [kw.pop(name, None) for name in ("q_bias", "k_bias", "v_bias", "cos_table", "sin_table")]
+    assert not kw, sorted(kw)
+    ref = ckr.chunk_kv8_model(tokens, k8, v8, seq_len, idx_layer, rot_dim, dtype, window, None, k_scale, v_scale, *bias_and_tables,
+                              scale)
+    return dict(o=ref["o"], q16=ref["q16"])
 
 
 # ---- problems (canonical cache layout [B, L, M, Hkv, D], uint8): made once, never modified -------------------------------
@@ -273,37 +253,13 @@ page_size, page_table = cw.page_size, cw.page_table
 def to_layout(c, layout, fill=FILL):
     """canonical uint8 numpy [B, L, M, Hkv, D] -> the (CPU) torch tensor of `layout`; the spare pages hold `fill`"""
     import torch
-    t = torch.from_numpy(np.ascontiguousarray(c))
-    nb, D = c.shape[0], c.shape[-1]
-    if layout == "blmhd":
-        return t.clone()
-    if layout == "blhmd":
-        return t.permute(0, 1, 3, 2, 4).contiguous()
-    ps = page_size(layout)
-    table, n = page_table(ps, nb)
-    pps = M // ps
-    pool = torch.full((n, L, ps, HKV, D), fill, dtype=torch.uint8)
-    pool[torch.from_numpy(table.reshape(-1)).long()] = (
-        t.view(nb, L, pps, ps, HKV, D).permute(0, 2, 1, 3, 4, 5).reshape(nb * pps, L, ps, HKV, D))
-    return pool
+    return cw.to_layout(torch.from_numpy(np.ascontiguousarray(c)), layout, fill)
 
 
 def from_layout(t, layout, nb):
     """(canonical uint8 numpy [B, L, M, Hkv, D], the spare pages as a tensor or None)"""
-    import torch
-    t = t.cpu().view(torch.uint8)
-    D = t.shape[-1]
-    if layout == "blmhd":
-        return t.numpy(), None
-    if layout == "blhmd":
-        return t.permute(0, 1, 3, 2, 4).contiguous().numpy(), None
-    ps = page_size(layout)
-    table, n = page_table(ps, nb)
-    pps = M // ps
-    own = torch.from_numpy(table.reshape(-1)).long()
-    rest = torch.from_numpy(np.setdiff1d(np.arange(n), table.reshape(-1))).long()
-    canon = t[own].view(nb, pps, L, ps, HKV, D).permute(0, 2, 1, 3, 4, 5).reshape(nb, L, M, HKV, D).contiguous()
-    return canon.numpy(), t[rest].contiguous()
+    canon, spare = cw.from_layout(t, layout, nb)
+    return canon.numpy(), spare
 
 
 # ---- the device ----------------------------------------------------------------------------------------------------------

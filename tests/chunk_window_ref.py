@@ -1,11 +1,11 @@
-"""fp64 reference, problems and device harness of sfa_decode_chunk_window / sfa_decode_varlen_window for
+"""Reference, problems and device harness of sfa_decode_chunk_window / sfa_decode_varlen_window for
 tests/test_decode_chunk_window_{cpu,gpu}.py and tests/test_decode_varlen_window_gpu.py.
 
-The reference is window_ref.decode_window_ref applied token by token, with the appended rows fed forward:
-chunk_window_ref_literal does exactly that.  chunk_window_ref computes the same thing a sequence at a time (the prologue
-of all tokens with the oracle's own rope_interleaved / round_to, then one masked fp64 softmax over the rows
-[lo_0, pos + n)); tests/test_decode_chunk_window_cpu.py holds the two together.  Rows below lo_0 = max(0, pos + 1 -
-window) are never looked at, so they may hold NaN.
+chunk_window_ref is an adapter over tests/serving_model.py, which holds the arithmetic: the prologue of all tokens, the
+append, then token t over the rows [lo_t, pos + t] of the cache after it.  chunk_window_ref_literal states the contract the
+other way -- window_ref.decode_window_ref applied token by token, with the appended rows fed forward -- and
+tests/test_decode_chunk_window_cpu.py holds the two together.  Rows below lo_0 = max(0, pos + 1 - window) are never looked
+at, so they may hold NaN.
 
 Shapes follow the constants of the kernel: a q-tile is 256 query rows (row r = t * G + g), a wave 32 rows, a key tile 64
 keys, a half-tile 32.
@@ -16,7 +16,8 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from oracle import rope_interleaved, rotary_table_ref, round_to
+import serving_model as sm
+from oracle import rotary_table_ref, round_to, to_bits16  # noqa: F401  (round_to: tests reach it through this module)
 from window_ref import TOL, decode_window_ref, window_lo  # noqa: F401
 
 QTILE, WAVE, KTILE, HALF = 256, 32, 64, 32
@@ -30,49 +31,25 @@ ULP = {"fp16": 2.0 ** -10, "bf16": 2.0 ** -7}
 
 # ---- the reference -----------------------------------------------------------------------------------------------------
 
+def chunk_window_model(prob, window, sinks=None, scale=None):
+    """A 16-bit problem (below) through the model, for chunk_window_ref and sinks_ref.chunk_sinks_ref: per sequence b
+    (o [n_b, H, D] float32 unrounded, k_rows, v_rows [n_b, Hkv, D] float32, lse [n_b, H] float64 without the sink, o in
+    float64).  LAYER alone of the float caches is turned into bits."""
+    f = lambda x: None if x is None else x.float().numpy()
+    cos, sin = rotary_tables(prob.dtype, prob.rot) if prob.tables and prob.rot > 0 else (None, None)
+    H = prob.G * getattr(prob, "Hkv", HKV)      # (a problem built by hand may have another kv-head count)
+    call = sm.make_call(prob.dtype, H, prob.lens, prob.ns, [f(prob.qkv[b][:n]) for b, n in enumerate(prob.ns)], 0, prob.rot,
+                        q_bias=f(prob.qb), k_bias=f(prob.kb), v_bias=f(prob.vb), cos=cos, sin=sin, window=window, sinks=sinks,
+                        softmax_scale=scale)
+    cache = tuple(to_bits16(c[:, LAYER:LAYER + 1], prob.dtype) for c in (prob.kf, prob.vf))
+    app, res = sm.run(cache, call)
+    return [(o.astype(np.float32), k16, v16, lse, o) for (o, lse), k16, v16 in zip(res, app["k16"], app["v16"])]
+
+
 def chunk_window_ref(prob, window):
     """prob: a problem (below).  Returns per sequence b (o [n_b, H, D] float32 unrounded, k_rows, v_rows [n_b, Hkv, D]
     float32 = what the call stores at the cache rows pos .. pos + n_b - 1).  window None: no window."""
-    D, G, H = prob.D, prob.G, prob.G * HKV
-    scale = 1.0 / np.sqrt(float(D))
-    f64 = lambda x: None if x is None else x.float().numpy().astype(np.float64)
-    qb, kb, vb = f64(prob.qb), f64(prob.kb), f64(prob.vb)
-    out = []
-    for b, (pos, n) in enumerate(zip(prob.lens, prob.ns)):
-        x = prob.qkv[b][:n].float().numpy().astype(np.float64)              # [n, H + 2 Hkv, D]
-        q, k, v = x[:, :H], x[:, H:H + HKV], x[:, H + HKV:]
-        if qb is not None:
-            q, k, v = q + qb, k + kb, v + vb
-        qr = np.empty_like(q)
-        kr = np.empty_like(k)
-        for t in range(n):
-            c = s = None
-            if prob.tables and prob.rot > 0:
-                cos, sin = rotary_tables(prob.dtype, prob.rot)
-                c, s = cos[pos + t], sin[pos + t]
-            qr[t] = rope_interleaved(q[t], pos + t, prob.rot, cos=c, sin=s)
-            kr[t] = rope_interleaved(k[t], pos + t, prob.rot, cos=c, sin=s)
-        qr = round_to(qr, prob.dtype).astype(np.float64)
-        k_rows, v_rows = round_to(kr, prob.dtype).astype(np.float32), round_to(v, prob.dtype).astype(np.float32)
-        if n == 0:
-            out.append((np.zeros((0, H, D), np.float32), k_rows, v_rows))
-            continue
-        lo0 = window_lo(pos, window)
-        K = np.concatenate([prob.kf[b, LAYER, lo0:pos].astype(np.float64), k_rows.astype(np.float64)])    # rows lo0 ..
-        V = np.concatenate([prob.vf[b, LAYER, lo0:pos].astype(np.float64), v_rows.astype(np.float64)])
-        j = lo0 + np.arange(K.shape[0])
-        t = np.arange(n)
-        lo_t = np.array([window_lo(pos + int(tt), window) for tt in t])
-        vis = (j[None, :] >= lo_t[:, None]) & (j[None, :] <= pos + t[:, None])                            # [n, keys]
-        q2 = qr.reshape(n, HKV, G, D).transpose(1, 2, 0, 3).reshape(HKV, G * n, D)
-        sc = np.matmul(q2, K.transpose(1, 2, 0)).reshape(HKV, G, n, -1) * scale                             # [k, g, t, j]
-        sc = np.where(vis[None, None], sc, -np.inf)
-        sc -= sc.max(axis=3, keepdims=True)
-        p = np.exp(sc)
-        p /= p.sum(axis=3, keepdims=True)
-        o = np.matmul(p.reshape(HKV, G * n, -1), V.transpose(1, 0, 2)).reshape(HKV, G, n, D).transpose(2, 0, 1, 3).reshape(n, H, D)
-        out.append((o.astype(np.float32), k_rows, v_rows))
-    return out
+    return [r[:3] for r in chunk_window_model(prob, window)]
 
 
 def chunk_window_ref_literal(prob, window):
@@ -294,7 +271,14 @@ def page_table(ps, B):
     return np.random.default_rng(3).permutation(n)[:B * pps].astype(np.int32).reshape(B, pps), n
 
 
+def storage(t):
+    """a tensor of a 16-bit or an 8-bit type as its storage integers"""
+    return t.contiguous().view(torch.int16 if t.element_size() == 2 else torch.uint8)
+
+
 def to_layout(c, layout, spare_bits=0):
+    """canonical [B, L, M, Hkv, D] of a 16-bit or an 8-bit type (chunk_kv8_window_ref: uint8) -> the tensor of `layout`;
+    the pages no sequence owns hold spare_bits"""
     B, D = c.shape[0], c.shape[-1]
     if layout == "blmhd":
         return c.clone()
@@ -303,15 +287,15 @@ def to_layout(c, layout, spare_bits=0):
     ps = page_size(layout)
     table, n = page_table(ps, B)
     pps = M // ps
-    pool = torch.full((n, L, ps, HKV, D), spare_bits, dtype=torch.int16).view(c.dtype)
+    pool = torch.full((n, L, ps, HKV, D), spare_bits, dtype=storage(c[:0]).dtype).view(c.dtype)
     pool[torch.from_numpy(table.reshape(-1)).long()] = (
         c.view(B, L, pps, ps, HKV, D).permute(0, 2, 1, 3, 4, 5).reshape(B * pps, L, ps, HKV, D))
     return pool
 
 
 def from_layout(t, layout, B):
-    """(canonical bits [B, L, M, Hkv, D], the bits of the spare pages or None)"""
-    t = bits(t.cpu())
+    """(canonical storage integers [B, L, M, Hkv, D], those of the spare pages or None)"""
+    t = storage(t.cpu())
     D = t.shape[-1]
     if layout == "blmhd":
         return t, None

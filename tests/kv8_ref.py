@@ -1,11 +1,12 @@
-"""CPU reference of the fp8 (OCP e4m3) KV cache, shared by the sfa_decode_kv8 / sfa_kv8_quantize tests: the code table,
-the quantiser of the header's contract, and one decode step in fp64 over the dequantised cache.
+"""CPU reference of the fp8 (OCP e4m3) KV cache, shared by the sfa_decode_kv8 / sfa_kv8_quantize tests: the code table, the
+quantiser of the header's contract, and one decode step over the dequantised cache, an adapter over tests/serving_model.py
+(which quantises and dequantises with the two functions here).
 
 e4m3: 1 sign, 4 exponent (bias 7), 3 mantissa bits, no infinities, 0x7F / 0xFF = NaN, largest finite 448 (0x7E): torch's
 float8_e4m3fn."""
 import numpy as np
 
-from oracle import rope_interleaved, round_to
+import serving_model as sm          # (imports this module for quantize / dequantize)
 
 
 def _table():
@@ -59,6 +60,25 @@ def step_at(v):
     return 2.0 ** (np.floor(np.log2(a)) - 3)
 
 
+def decode_kv8_model(qkv, k8, v8, seq_len, idx_layer, rot_dim, dtype, window, sinks, k_scale, v_scale, q_bias, k_bias, v_bias,
+                     cos_table, sin_table, scale):
+    """The single-token call over an fp8 cache through the model, for decode_kv8_ref, kv8_window_ref.decode_kv8_window_ref
+    and kv8_sinks_ref.decode_kv8_sinks_ref.  k8 / v8 are MUTATED.  Returns dict(o, k_row, v_row, o64, lse, q16)."""
+    qkv = np.asarray(qkv)
+    M = k8.shape[2]
+    for b, pos in enumerate(seq_len):
+        if not (0 <= int(pos) < M):
+            raise ValueError(f"seq_len[{b}]={int(pos)} outside [0, memory_max_len={M})")
+    call = sm.make_call(dtype, qkv.shape[1] - 2 * k8.shape[3], seq_len, [1] * len(qkv), [x[None] for x in qkv], idx_layer, rot_dim,
+                        q_bias=q_bias, k_bias=k_bias, v_bias=v_bias, cos=cos_table, sin=sin_table, window=window, sinks=sinks,
+                        k_scale=k_scale, v_scale=v_scale, softmax_scale=scale)
+    app, res = sm.run((k8, v8), call, in_place=True)
+    first = lambda xs: np.stack([x[0] for x in xs])
+    o = first(r[0] for r in res)
+    return dict(o=o.astype(np.float32), k_row=first(app["k_bits"]), v_row=first(app["v_bits"]), o64=o,
+                lse=first(r[1] for r in res), q16=first(app["q16"]))
+
+
 def decode_kv8_ref(qkv, k8, v8, seq_len, idx_layer, rot_dim, dtype, k_scale=None, v_scale=None, q_bias=None,
                    k_bias=None, v_bias=None, cos_table=None, sin_table=None, scale=None):
     """One sfa_decode_kv8 step for the whole batch.
@@ -70,46 +90,6 @@ def decode_kv8_ref(qkv, k8, v8, seq_len, idx_layer, rot_dim, dtype, k_scale=None
 
     k16 / v16 are what sfa_decode would store (bias, RoPE, rounded to `dtype`); the stored bytes are q8(x16 / scale);
     the attention runs in fp64 over scale * (the bytes of rows 0 .. pos), the new row included."""
-    qkv = np.asarray(qkv)
-    B, HH, D = qkv.shape
-    Hkv = k8.shape[3]
-    H = HH - 2 * Hkv
-    G = H // Hkv
-    M = k8.shape[2]
-    if scale is None:
-        scale = 1.0 / np.sqrt(float(D))
-    ks = np.ones(Hkv, np.float32) if k_scale is None else np.asarray(k_scale, dtype=np.float32)
-    vs = np.ones(Hkv, np.float32) if v_scale is None else np.asarray(v_scale, dtype=np.float32)
-    o = np.zeros((B, H, D), dtype=np.float64)
-    k_rows = np.zeros((B, Hkv, D), dtype=np.uint8)
-    v_rows = np.zeros((B, Hkv, D), dtype=np.uint8)
-    for b in range(B):
-        pos = int(seq_len[b])
-        if not (0 <= pos < M):
-            raise ValueError(f"seq_len[{b}]={pos} outside [0, memory_max_len={M})")
-        q = qkv[b, :H].astype(np.float64)
-        k = qkv[b, H:H + Hkv].astype(np.float64)
-        v = qkv[b, H + Hkv:].astype(np.float64)
-        if q_bias is not None:
-            q = q + np.asarray(q_bias, dtype=np.float64)
-        if k_bias is not None:
-            k = k + np.asarray(k_bias, dtype=np.float64)
-        if v_bias is not None:
-            v = v + np.asarray(v_bias, dtype=np.float64)
-        c = s = None
-        if cos_table is not None and rot_dim > 0:
-            c, s = cos_table[pos], sin_table[pos]
-        q16 = round_to(rope_interleaved(q, pos, rot_dim, cos=c, sin=s), dtype).astype(np.float64)
-        k16 = round_to(rope_interleaved(k, pos, rot_dim, cos=c, sin=s), dtype)
-        v16 = round_to(v, dtype)
-        k8[b, idx_layer, pos] = k_rows[b] = quantize(k16, ks)
-        v8[b, idx_layer, pos] = v_rows[b] = quantize(v16, vs)
-        K = dequantize(k8[b, idx_layer, :pos + 1], ks)          # [T, Hkv, D]
-        V = dequantize(v8[b, idx_layer, :pos + 1], vs)
-        K, V = np.repeat(K, G, axis=1), np.repeat(V, G, axis=1)
-        sc = np.einsum("hd,thd->ht", q16, K) * scale
-        sc -= sc.max(axis=1, keepdims=True)
-        p = np.exp(sc)
-        p /= p.sum(axis=1, keepdims=True)
-        o[b] = np.einsum("ht,thd->hd", p, V)
-    return dict(o=o.astype(np.float32), k_row=k_rows, v_row=v_rows)
+    ref = decode_kv8_model(qkv, k8, v8, seq_len, idx_layer, rot_dim, dtype, None, None, k_scale, v_scale, q_bias, k_bias, v_bias,
+                           cos_table, sin_table, scale)
+    return {key: ref[key] for key in ("o", "k_row", "v_row")}

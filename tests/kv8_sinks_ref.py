@@ -1,4 +1,4 @@
-"""fp64 references of sfa_decode_kv8_window_sinks / sfa_decode_chunk_kv8_window_sinks / sfa_decode_varlen_kv8_window_sinks
+"""References of sfa_decode_kv8_window_sinks / sfa_decode_chunk_kv8_window_sinks / sfa_decode_varlen_kv8_window_sinks
 (attention sinks in the three windowed decode calls over an fp8 e4m3 KV cache) for tests/test_decode_kv8_sinks_{cpu,gpu}.py.
 
 An attention sink is one more key of every softmax of query head h, with logit sinks[h] (natural-log units, multiplied
@@ -7,11 +7,10 @@ row's key range [lo, pos]:
 
     o[h] = v_scale[hk] sum_j exp(s_j) V8_j / (exp(sinks[h]) + sum_j exp(s_j))
 
-The prologue and the quantised append are taken exactly as kv8_window_ref.decode_kv8_window_ref and
-chunk_kv8_window_ref.chunk_kv8_window_ref take them (they are called), and the attention is chunk_kv8_window_ref.attend
-over the cache bytes after the append with the sink column added: with every sink -inf attend_sinks() performs the same
-floating-point operations as attend() and returns the same numbers, exactly.  Each reference also returns the row's
-log-sum-exp WITHOUT the sink, from which the tests build sinks of a known weight (sinks_ref.make_sinks):
+The functions here are adapters over tests/serving_model.py, which holds this arithmetic, as kv8_window_ref.
+decode_kv8_window_ref and chunk_kv8_window_ref.chunk_kv8_window_ref are: with every sink -inf (or sinks None) the model
+performs the operations of the call without sinks and returns the same numbers, exactly.  Each reference also returns the
+row's log-sum-exp WITHOUT the sink, from which the tests build sinks of a known weight (sinks_ref.make_sinks):
 
     sinks[h] = lse[anchor, h] + delta_h   =>   the sink's share of the anchor row's softmax is sigmoid(delta_h)
 
@@ -28,7 +27,6 @@ import chunk_kv8_ref as ckr
 import chunk_kv8_window_ref as ckw
 import kv8_ref
 import kv8_window_ref as kwr
-from oracle import rope_interleaved, round_to
 from sinks_ref import deltas, make_sinks, sigmoid  # noqa: F401  (re-exported for the two test files)
 from window_ref import TOL, window_lo  # noqa: F401
 
@@ -36,69 +34,21 @@ B, HKV, L, M, LAYER, LENS = ckw.B, ckw.HKV, ckw.L, ckw.M, ckw.LAYER, ckw.LENS
 assert (kwr.B, kwr.HKV, kwr.L, kwr.M, kwr.LAYER, kwr.LENS) == (B, HKV, L, M, LAYER, LENS)
 
 
-def _sink_f64(sinks, H):
-    s = np.full(H, -np.inf) if sinks is None else np.asarray(sinks, np.float64)
-    assert s.shape == (H,)
-    return s
-
-
 def attend_sinks(q16, k8, v8, pos, window, sinks, k_scale=None, v_scale=None, scale=None):
     """chunk_kv8_window_ref.attend with a sink column: q16 [n, H, D] float64 rotated, rounded queries of the tokens at
     pos .. pos + n - 1 of one sequence; k8 / v8 [M, Hkv, D] uint8, one (sequence, layer) of the cache after the append;
     sinks [H] (None = all -inf).  Returns (o [n, H, D] float64, lse [n, H] float64 = log sum_j exp(s_j) over the row's
     key range, without the sink)."""
-    n, H, D = q16.shape
-    Hkv = k8.shape[1]
-    G = H // Hkv
-    if scale is None:
-        scale = 1.0 / np.sqrt(float(D))
-    ks = np.ones(Hkv, np.float32) if k_scale is None else np.asarray(k_scale, dtype=np.float32)
-    vs = np.ones(Hkv, np.float32) if v_scale is None else np.asarray(v_scale, dtype=np.float32)
-    sk = _sink_f64(sinks, H)[:, None]
-    o = np.zeros((n, H, D), dtype=np.float64)
-    lse = np.zeros((n, H), dtype=np.float64)
-    for t in range(n):
-        lo = window_lo(pos + t, window)
-        K = kv8_ref.dequantize(k8[lo:pos + t + 1], ks)
-        V = kv8_ref.dequantize(v8[lo:pos + t + 1], vs)
-        K, V = np.repeat(K, G, axis=1), np.repeat(V, G, axis=1)
-        sc = np.einsum("hd,thd->ht", q16[t], K) * scale
-        m0 = sc.max(axis=1, keepdims=True)
-        lse[t] = (m0 + np.log(np.exp(sc - m0).sum(axis=1, keepdims=True)))[:, 0]
-        sc -= np.maximum(m0, sk)
-        p = np.exp(sc)
-        p /= p.sum(axis=1, keepdims=True) + np.exp(sk - np.maximum(m0, sk))
-        o[t] = np.einsum("ht,thd->hd", p, V)
-    return o, lse
+    return ckr.attend_bytes(q16, k8, v8, pos, window, sinks, k_scale, v_scale, scale)
 
 
 def decode_kv8_sinks_ref(qkv, k8, v8, seq_len, idx_layer, rot_dim, dtype, window, sinks, k_scale=None, v_scale=None,
                          q_bias=None, k_bias=None, v_bias=None, cos_table=None, sin_table=None, scale=None):
-    """kv8_window_ref.decode_kv8_window_ref with sinks [H] (None = all -inf); k8 / v8 are MUTATED at the appended rows, by
-    that function.  Returns its dict with o replaced (float32, unrounded) plus o64, lse [B, H] float64 without the sink and
-    q16 [B, H, D] float64 = the rotated, rounded queries."""
-    qkv = np.asarray(qkv)
-    Bn, HH, D = qkv.shape
-    H = HH - 2 * k8.shape[3]
-    with np.errstate(invalid="ignore"):         # (a 0x7F below the window makes the base's o NaN only where window is None)
-        base = kwr.decode_kv8_window_ref(qkv, k8, v8, seq_len, idx_layer, rot_dim, dtype, window, k_scale, v_scale,
-                                         q_bias=q_bias, k_bias=k_bias, v_bias=v_bias, cos_table=cos_table,
-                                         sin_table=sin_table, scale=scale)
-    o = np.zeros((Bn, H, D), np.float64)
-    lse = np.zeros((Bn, H), np.float64)
-    q16 = np.zeros((Bn, H, D), np.float64)
-    for b in range(Bn):
-        pos = int(seq_len[b])
-        q = qkv[b, :H].astype(np.float64)       # the query's prologue, as decode_kv8_window_ref has it
-        if q_bias is not None:
-            q = q + np.asarray(q_bias, dtype=np.float64)
-        c = s = None
-        if cos_table is not None and rot_dim > 0:
-            c, s = cos_table[pos], sin_table[pos]
-        q16[b] = round_to(rope_interleaved(q, pos, rot_dim, cos=c, sin=s), dtype).astype(np.float64)
-        ob, lb = attend_sinks(q16[b][None], k8[b, idx_layer], v8[b, idx_layer], pos, window, sinks, k_scale, v_scale, scale)
-        o[b], lse[b] = ob[0], lb[0]
-    return dict(base, o=o.astype(np.float32), o64=o, lse=lse, q16=q16)
+    """kv8_window_ref.decode_kv8_window_ref with sinks [H] (None = all -inf); k8 / v8 are MUTATED at the appended rows.
+    Returns its dict (o float32, unrounded) plus o64, lse [B, H] float64 without the sink and q16 [B, H, D] float64 = the
+    rotated, rounded queries."""
+    return kv8_ref.decode_kv8_model(qkv, k8, v8, seq_len, idx_layer, rot_dim, dtype, window, sinks, k_scale, v_scale, q_bias,
+                                    k_bias, v_bias, cos_table, sin_table, scale)
 
 
 def chunk_kv8_sinks_ref(p, window, sinks, lens=None, base=None):

@@ -1,10 +1,10 @@
-"""fp64 reference of sfa_decode_kv8_window (sliding-window decode over an fp8 e4m3 KV cache) and the problems of
+"""Reference of sfa_decode_kv8_window (sliding-window decode over an fp8 e4m3 KV cache) and the problems of
 tests/test_decode_kv8_window_{cpu,gpu}.py.
 
-The reference is kv8_ref.decode_kv8_ref with a lower bound: the same prologue (bias, RoPE, rounding to the 16-bit dtype),
-the same quantisation of the new token into the caches, then the fp64 softmax over the rows [lo, pos] of the DEQUANTISED
-cache, lo = max(0, pos + 1 - window).  Rows below lo are never looked at, so they may hold the NaN byte 0x7F.  window =
-None, or any window > pos, is kv8_ref.decode_kv8_ref itself: the same operations in the same order, the same bits.
+The reference is kv8_ref.decode_kv8_ref with a lower bound, through the same adapter over tests/serving_model.py: the
+prologue, the quantisation of the new token into the caches, then the fp64 softmax over the rows [lo, pos] of the
+DEQUANTISED cache, lo = max(0, pos + 1 - window).  Rows below lo are never looked at, so they may hold the NaN byte 0x7F.
+window = None, or any window > pos, gives kv8_ref.decode_kv8_ref's bits.
 
 Because the reference sees the dequantised bytes the device sees, the quantisation error is on both sides and the
 project's decode tolerances (window_ref.TOL) apply unchanged.
@@ -16,7 +16,7 @@ import numpy as np
 
 import decode_cases as dc
 import kv8_ref
-from oracle import rope_interleaved, rotary_table_ref, round_to
+from oracle import rotary_table_ref, round_to
 from window_ref import TOL, window_lo  # noqa: F401  (TOL: re-exported for the two test files)
 
 
@@ -24,50 +24,9 @@ def decode_kv8_window_ref(qkv, k8, v8, seq_len, idx_layer, rot_dim, dtype, windo
                           q_bias=None, k_bias=None, v_bias=None, cos_table=None, sin_table=None, scale=None):
     """One sfa_decode_kv8_window step for the whole batch; the arguments and the result of kv8_ref.decode_kv8_ref, plus
     `window` (None = no window).  k8 / v8 [B, L, M, Hkv, D] uint8 are MUTATED at [b, idx_layer, seq_len[b]]."""
-    qkv = np.asarray(qkv)
-    B, HH, D = qkv.shape
-    Hkv = k8.shape[3]
-    H = HH - 2 * Hkv
-    G = H // Hkv
-    M = k8.shape[2]
-    if scale is None:
-        scale = 1.0 / np.sqrt(float(D))
-    ks = np.ones(Hkv, np.float32) if k_scale is None else np.asarray(k_scale, dtype=np.float32)
-    vs = np.ones(Hkv, np.float32) if v_scale is None else np.asarray(v_scale, dtype=np.float32)
-    o = np.zeros((B, H, D), dtype=np.float64)
-    k_rows = np.zeros((B, Hkv, D), dtype=np.uint8)
-    v_rows = np.zeros((B, Hkv, D), dtype=np.uint8)
-    for b in range(B):
-        pos = int(seq_len[b])
-        if not (0 <= pos < M):
-            raise ValueError(f"seq_len[{b}]={pos} outside [0, memory_max_len={M})")
-        q = qkv[b, :H].astype(np.float64)
-        k = qkv[b, H:H + Hkv].astype(np.float64)
-        v = qkv[b, H + Hkv:].astype(np.float64)
-        if q_bias is not None:
-            q = q + np.asarray(q_bias, dtype=np.float64)
-        if k_bias is not None:
-            k = k + np.asarray(k_bias, dtype=np.float64)
-        if v_bias is not None:
-            v = v + np.asarray(v_bias, dtype=np.float64)
-        c = s = None
-        if cos_table is not None and rot_dim > 0:
-            c, s = cos_table[pos], sin_table[pos]
-        q16 = round_to(rope_interleaved(q, pos, rot_dim, cos=c, sin=s), dtype).astype(np.float64)
-        k16 = round_to(rope_interleaved(k, pos, rot_dim, cos=c, sin=s), dtype)
-        v16 = round_to(v, dtype)
-        k8[b, idx_layer, pos] = k_rows[b] = kv8_ref.quantize(k16, ks)
-        v8[b, idx_layer, pos] = v_rows[b] = kv8_ref.quantize(v16, vs)
-        lo = window_lo(pos, window)
-        K = kv8_ref.dequantize(k8[b, idx_layer, lo:pos + 1], ks)        # [pos + 1 - lo, Hkv, D]
-        V = kv8_ref.dequantize(v8[b, idx_layer, lo:pos + 1], vs)
-        K, V = np.repeat(K, G, axis=1), np.repeat(V, G, axis=1)
-        sc = np.einsum("hd,thd->ht", q16, K) * scale
-        sc -= sc.max(axis=1, keepdims=True)
-        p = np.exp(sc)
-        p /= p.sum(axis=1, keepdims=True)
-        o[b] = np.einsum("ht,thd->hd", p, V)
-    return dict(o=o.astype(np.float32), k_row=k_rows, v_row=v_rows)
+    ref = kv8_ref.decode_kv8_model(qkv, k8, v8, seq_len, idx_layer, rot_dim, dtype, window, None, k_scale, v_scale, q_bias, k_bias,
+                                   v_bias, cos_table, sin_table, scale)
+    return {key: ref[key] for key in ("o", "k_row", "v_row")}
 
 
 # The parity sweep of tests/test_decode_kv8_window_gpu.py: (dtype, head_dim, layout, group, num_splits, window), a

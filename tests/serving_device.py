@@ -10,9 +10,9 @@ import serving_cases as sc
 import serving_model as sm
 from chunk_window_ref import ULP
 from oracle import from_bits16
+from window_ref import TOL          # the project's decode tolerances, atol = rtol
 
-TOL = {"fp16": 2e-3, "bf16": 1.6e-2}            # the project's decode tolerances (chunk_kv8_ref.check_o), atol = rtol
-TDT = {"fp16": torch.float16, "bf16": torch.bfloat16}
+TDT ={"fp16": torch.float16, "bf16": torch.bfloat16}
 FILL = 7.0                                      # what o holds before a call
 
 

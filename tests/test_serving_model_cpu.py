@@ -1,27 +1,32 @@
 """CPU tests of tests/serving_model.py (the geometry-free fp64 model of a decode call) and tests/serving_cases.py (the
 seeded generators of the serving traces and of the prefill fuzz).
 
-1. Anchors: at the geometries of the existing references the model agrees with each of them -- o to 1e-9 where the
-   reference keeps fp64, to the bit after rounding to float32 where it returns float32; appended rows and bytes identical.
+1. Anchors.  The model against oracle.decode_ref, computed here.  The reference functions of the *_ref.py files, which are
+   adapters over the model, against what each of them returned while it had arithmetic of its own, recorded in
+   tests/golden/decode_ref_anchors.npz (decode_ref_anchor_cases.py and make_decode_ref_anchors.py beside it): o to 1e-9
+   where the function keeps fp64, to the bit after rounding to float32 where it returns float32; appended rows, bytes and
+   the hashes of the caches identical.
 2. Coverage: every item the traces and the prefill cases must reach is listed with a seed that reaches it, so that a change
    to a generator cannot silently drop one.
 3. The generators are deterministic, every generated call satisfies the header's preconditions, and the reference alone
    meets the conditions the fp8 byte checks lean on at every committed seed.
 """
 import functools
+import importlib.util
+import os
 
 import numpy as np
 import pytest
 
-import chunk_kv8_ref as ckr
-import chunk_kv8_window_ref as ckw
-import chunk_window_ref as cw
-import kv8_sinks_ref as k8s
 import serving_cases as sc
 import serving_model as sm
-import sinks_ref
+from conftest import GOLDEN, load_golden
 from oracle import decode_ref, round_to, rotary_table_ref, to_bits16
-from window_ref import decode_window_ref
+
+RECORDED = load_golden("decode_ref_anchors.npz")
+_spec = importlib.util.spec_from_file_location("decode_ref_anchor_cases", os.path.join(GOLDEN, "decode_ref_anchor_cases.py"))
+anchors = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(anchors)
 
 
 def same_f32(model_o, ref_o):
@@ -56,111 +61,27 @@ def test_anchor_decode_ref(dtype, rot, tables, bias):
         same_f32(o[b][0], ref["o"][b])
 
 
-def _call16(prob, window=None, sinks=None, n=None):
-    """the model call and cache of a chunk_window_ref problem"""
-    f = lambda x: None if x is None else x.float().numpy()
-    cos, sin = cw.rotary_tables(prob.dtype, prob.rot) if prob.tables and prob.rot > 0 else (None, None)
-    ns = prob.ns if n is None else (n,) * prob.B
-    call = sm.make_call(prob.dtype, prob.H, prob.lens, ns, [prob.qkv[b, :k].float().numpy() for b, k in enumerate(ns)],
-                        cw.LAYER, prob.rot, q_bias=f(prob.qb), k_bias=f(prob.kb), v_bias=f(prob.vb), cos=cos, sin=sin,
-                        window=window, sinks=sinks)
-    return call, (to_bits16(prob.kf, prob.dtype), to_bits16(prob.vf, prob.dtype))
+def test_the_fixture_records_every_case_and_nothing_else():
+    assert {k.rsplit("/", 1)[0] for k in RECORDED.files if k != "commit"} == set(anchors.CASES)
+    assert len(str(RECORDED["commit"])) == 40
+    functions = {name.split("/")[0] for name in anchors.CASES}
+    assert len(functions) == 11 and all(sum(n.startswith(f + "/") for n in anchors.CASES) >= 2 for f in functions)
 
 
-@pytest.mark.parametrize("dtype,G,window", [("fp16", 1, 100), ("bf16", 4, 1), ("fp16", 8, 5000)])
-def test_anchor_decode_window_ref(dtype, G, window):
-    prob = cw.problem(dtype, 64, G, 1)
-    f = lambda x: x.float().numpy()
-    x = f(prob.qkv[:, 0])
-    ref = decode_window_ref(x[:, :prob.H], x[:, prob.H:prob.H + cw.HKV], x[:, prob.H + cw.HKV:], prob.kf, prob.vf, prob.lens,
-                            cw.LAYER, prob.rot, window, dtype, q_bias=f(prob.qb), k_bias=f(prob.kb), v_bias=f(prob.vb))
-    call, cache = _call16(prob, window)
-    app, attend = sm.step(cache, call)
-    o = attend(*sm.apply(cache, call, app))
-    for b in range(prob.B):
-        np.testing.assert_array_equal(app["k16"][b][0], ref["k_row"][b])
-        np.testing.assert_array_equal(app["v16"][b][0], ref["v_row"][b])
-        same_f32(o[b][0], ref["o"][b])
-
-
-@pytest.mark.parametrize("dtype,D,G,n,window,tables", [("bf16", 64, 2, 5, 3, False), ("fp16", 128, 1, 7, 130, True),
-                                                       ("fp16", 64, 16, 3, 5000, False)])
-def test_anchor_chunk_window_ref_literal(dtype, D, G, n, window, tables):
-    prob = cw.problem(dtype, D, G, n, tables)
-    ref = cw.chunk_window_ref_literal(prob, window)
-    call, cache = _call16(prob, window)
-    app, attend = sm.step(cache, call)
-    o = attend(*sm.apply(cache, call, app))
-    for b in range(prob.B):
-        np.testing.assert_array_equal(app["k16"][b], ref[b][1])
-        np.testing.assert_array_equal(app["v16"][b], ref[b][2])
-        same_f32(o[b], ref[b][0])
-
-
-@pytest.mark.parametrize("dtype,D,G,window", [("fp16", 64, 4, 4), ("bf16", 128, 2, 200)])
-def test_anchor_chunk_sinks_ref(dtype, D, G, window):
-    """ragged token counts (an empty sequence among them) and a sink of -inf"""
-    prob = cw.make_problem(dtype, D, G, cw.LENS, (6, 0, 1, 9), seed=3)
-    sinks = np.linspace(-2.0, 3.0, prob.H)
-    sinks[1] = -np.inf
-    ref = sinks_ref.chunk_sinks_ref(prob, window, sinks)
-    call, cache = _call16(prob, window, sinks)
-    app, attend = sm.step(cache, call)
-    o = attend(*sm.apply(cache, call, app))
-    for b in range(prob.B):
-        np.testing.assert_array_equal(app["k16"][b], ref[b][1])
-        np.testing.assert_array_equal(app["v16"][b], ref[b][2])
-        np.testing.assert_allclose(o[b], ref[b][4], atol=1e-9, rtol=0)
-        same_f32(o[b], ref[b][0])
-
-
-def _call8(p, window=None, sinks=None):
-    """the model call and cache of a chunk_kv8_window_ref problem"""
-    cos, sin = ckw.rotary_tables(p.dtype, p.rot) if p.tables and p.rot > 0 else (None, None)
-    qb, kb, vb = (None, None, None) if p.biases is None else p.biases
-    call = sm.make_call(p.dtype, p.H, p.lens, p.ns, p.tok, ckw.LAYER, p.rot, q_bias=qb, k_bias=kb, v_bias=vb, cos=cos, sin=sin,
-                        window=window, sinks=sinks, k_scale=p.ks, v_scale=p.vs, softmax_scale=p.scale)
-    return call, (p.k8, p.v8)
-
-
-def _check8(call, cache, ref_o, k_ref, v_ref):
-    app, attend = sm.step(cache, call)
-    after = sm.apply(cache, call, app)
-    np.testing.assert_array_equal(after[0], k_ref)              # every byte of both caches after the call
-    np.testing.assert_array_equal(after[1], v_ref)
-    o = attend(*after)
-    for b, want in enumerate(ref_o):
-        np.testing.assert_allclose(o[b], want, atol=1e-9, rtol=0)
-
-
-@pytest.mark.parametrize("dtype,G,rot,bias", [("fp16", 4, 128, False), ("bf16", 1, 64, True)])
-def test_anchor_chunk_kv8_ref(dtype, G, rot, bias):
-    """chunk_kv8_ref at its own frame: L, M, LAYER = 2, 256, 1, amax scales times (0.5, 2), ragged counts"""
-    pr = ckr.make_problem(5, [3, 0, 8], 2, G, 128, dtype, scale_factors=(0.5, 2.0))
-    lens = [0, 100, 248]
-    rng = np.random.default_rng(6)
-    biases = tuple(round_to(rng.standard_normal((h, 128)), dtype) for h in (pr["H"], 2, 2)) if bias else None
-    ref, k_ref, v_ref = ckr.reference(pr, lens, rot=rot, biases=biases)
-    qb, kb, vb = biases or (None, None, None)
-    call = sm.make_call(dtype, pr["H"], lens, pr["counts"], pr["tok"], ckr.LAYER, rot, q_bias=qb, k_bias=kb, v_bias=vb,
-                        k_scale=pr["ks"], v_scale=pr["vs"])
-    _check8(call, (pr["k8"], pr["v8"]), ref["o"], k_ref, v_ref)
-
-
-@pytest.mark.parametrize("dtype,D,G,window", [("fp16", 64, 2, 3), ("bf16", 128, 8, 140)])
-def test_anchor_chunk_kv8_window_ref(dtype, D, G, window):
-    p = ckw.make_problem(dtype, D, G, ckw.LENS, (4, 0, 7, 2), seed=1, k_factors=(0.5, 2.0))
-    ref, k_ref, v_ref = ckw.reference(p, window)
-    _check8(*_call8(p, window), ref["o"], k_ref, v_ref)
-
-
-@pytest.mark.parametrize("dtype,D,G,window", [("bf16", 64, 4, 4), ("fp16", 128, 1, 1000)])
-def test_anchor_chunk_kv8_sinks_ref(dtype, D, G, window):
-    p = ckw.make_problem(dtype, D, G, ckw.LENS, (5, 1, 0, 3), seed=2, k_factors=(2.0, 0.5), tables=True)
-    sinks = np.linspace(3.0, -2.0, p.H).astype(np.float32)
-    sinks[0] = -np.inf
-    ref, k_ref, v_ref = k8s.chunk_kv8_sinks_ref(p, window, sinks)
-    _check8(*_call8(p, window, sinks), ref["o"], k_ref, v_ref)
+@pytest.mark.parametrize("name", list(anchors.CASES))
+def test_anchor_recorded(name):
+    """one case of the fixture on today's reference function: every field it returned, by the type it was returned in"""
+    got = anchors.CASES[name]()
+    assert {name + "/" + field for field in got} == {k for k in RECORDED.files if k.startswith(name + "/")}
+    for field, value in got.items():
+        want, value = RECORDED[name + "/" + field], np.asarray(value)
+        assert value.dtype == want.dtype and value.shape == want.shape, field
+        if want.dtype == np.float64:
+            np.testing.assert_allclose(value, want, atol=1e-9, rtol=0, err_msg=field)
+        elif want.dtype == np.float32:
+            same_f32(value, want)
+        else:                                                   # appended bytes, the hashes of the caches
+            np.testing.assert_array_equal(value, want, err_msg=field)
 
 
 # ---- 2. coverage -----------------------------------------------------------------------------------------------------------

@@ -1,21 +1,36 @@
-"""fp64 reference of sfa_decode_window for tests/test_decode_window_{cpu,gpu}.py.
-
-The new token's rotated q, and the k and v rows the call appends, come from oracle.decode_ref (bias, RoPE, rounding to
-the storage dtype: everything sfa_decode does before the attention).  The attention itself is done here, over the rows
-[lo, pos] of the caches the device was given plus the new row, lo = max(0, pos + 1 - window): the rows below lo are
-never looked at, so they may hold NaN.  window=None is plain sfa_decode.
+"""Reference of sfa_decode_window for tests/test_decode_window_{cpu,gpu}.py: an adapter over tests/serving_model.py, which
+holds the arithmetic (the prologue of the new token, the fp64 softmax over the rows [lo, pos] of the cache after the
+append, lo = max(0, pos + 1 - window)).  The rows below lo are never looked at, so they may hold NaN.  window=None is plain
+sfa_decode.
 
 Grouped queries are native: q has H heads, k / v and the caches Hkv, query head h reads kv head h // (H // Hkv).
 """
 import numpy as np
 
-from oracle import decode_ref
+import serving_model as sm          # (imports this module for window_lo)
+from oracle import to_bits16
 
-TOL = {"fp16": 2e-3, "bf16": 1.6e-2}          # the project's decode tolerances (tests/test_decode_gpu.py)
+TOL = {"fp16": 2e-3, "bf16": 1.6e-2}          # the project's decode tolerances (tests/test_decode_gpu.py), atol = rtol
 
 
 def window_lo(pos, window):
     return 0 if window is None else max(0, pos + 1 - int(window))
+
+
+def decode_window_model(q, k, v, k_cache, v_cache, seq_len, idx_layer, rot_dim, window, sinks, dtype, q_bias, k_bias, v_bias,
+                        cos_table, sin_table, scale):
+    """The 16-bit single-token call through the model, for decode_window_ref and sinks_ref.decode_window_sinks_ref: float
+    caches [B, L, M, Hkv, D] representable in dtype (idx_layer alone is turned into bits).  Returns dict(o, k_row, v_row,
+    lse, o64)."""
+    q, k, v = (np.asarray(x, np.float32) for x in (q, k, v))
+    call = sm.make_call(dtype, q.shape[1], seq_len, [1] * len(q), [np.concatenate(x)[None] for x in zip(q, k, v)], 0, rot_dim,
+                        q_bias=q_bias, k_bias=k_bias, v_bias=v_bias, cos=cos_table, sin=sin_table, window=window, sinks=sinks,
+                        softmax_scale=scale)
+    cache = tuple(to_bits16(np.asarray(c)[:, idx_layer:idx_layer + 1], dtype) for c in (k_cache, v_cache))
+    app, res = sm.run(cache, call)
+    o = np.stack([r[0][0] for r in res])
+    return dict(o=o.astype(np.float32), k_row=np.stack([x[0] for x in app["k16"]]), v_row=np.stack([x[0] for x in app["v16"]]),
+                lse=np.stack([r[1][0] for r in res]), o64=o)
 
 
 def decode_window_ref(q, k, v, k_cache, v_cache, seq_len, idx_layer, rot_dim, window, dtype="fp16",
@@ -23,36 +38,9 @@ def decode_window_ref(q, k, v, k_cache, v_cache, seq_len, idx_layer, rot_dim, wi
     """q [B, H, D], k / v [B, Hkv, D], caches [B, L, M, Hkv, D] (float, representable in `dtype`; not modified),
     biases [H, D] / [Hkv, D] / [Hkv, D].  Returns dict(o [B, H, D] float32 unrounded, k_row, v_row [B, Hkv, D] float32 =
     what the call stores at cache row seq_len[b])."""
-    q, k, v = (np.asarray(x, np.float32) for x in (q, k, v))
-    B, H, D = q.shape
-    Hkv = k.shape[1]
-    G = H // Hkv
-    assert G * Hkv == H
-    if scale is None:
-        scale = 1.0 / np.sqrt(float(D))
-    rep = lambda x: None if x is None else np.repeat(np.asarray(x, np.float32), G, axis=0)
-    o = np.zeros((B, H, D), np.float64)
-    k_rows = np.zeros((B, Hkv, D), np.float32)
-    v_rows = np.zeros((B, Hkv, D), np.float32)
-    for b in range(B):
-        pos = int(seq_len[b])
-        # the prologue, on the problem expanded to one kv head per query head; decode_ref's own attention runs over a
-        # cache that holds the new row only (its result is not used)
-        qkv_x = np.stack([q[b], np.repeat(k[b], G, axis=0), np.repeat(v[b], G, axis=0)])[None]
-        dummy_k = np.zeros((1, 1, pos + 1, H, D), np.float32)
-        pro = decode_ref(qkv_x, dummy_k, np.zeros_like(dummy_k), [pos], 0, rot_dim, dtype=dtype, q_bias=q_bias,
-                         k_bias=rep(k_bias), v_bias=rep(v_bias), cos_table=cos_table, sin_table=sin_table)
-        k_rows[b], v_rows[b] = pro["k_row"][0, ::G], pro["v_row"][0, ::G]
-        lo = window_lo(pos, window)
-        K = np.concatenate([np.asarray(k_cache[b, idx_layer, lo:pos], np.float64), k_rows[b][None].astype(np.float64)])
-        V = np.concatenate([np.asarray(v_cache[b, idx_layer, lo:pos], np.float64), v_rows[b][None].astype(np.float64)])
-        qr = pro["q_rot"][0].astype(np.float64).reshape(Hkv, G, D)
-        sc = np.einsum("kgd,tkd->kgt", qr, K) * scale
-        sc -= sc.max(axis=2, keepdims=True)
-        p = np.exp(sc)
-        p /= p.sum(axis=2, keepdims=True)
-        o[b] = np.einsum("kgt,tkd->kgd", p, V).reshape(H, D)
-    return dict(o=o.astype(np.float32), k_row=k_rows, v_row=v_rows)
+    ref = decode_window_model(q, k, v, k_cache, v_cache, seq_len, idx_layer, rot_dim, window, None, dtype, q_bias, k_bias,
+                              v_bias, cos_table, sin_table, scale)
+    return {key: ref[key] for key in ("o", "k_row", "v_row")}
 
 
 # The parity sweep of tests/test_decode_window_gpu.py: (dtype, head_dim, layout, group, num_splits, window), a pairwise-
