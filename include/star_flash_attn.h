@@ -570,6 +570,67 @@ int sfa_decode_varlen_kv8_window_sinks(const sfa_decode_args *args, const float 
                                        const float *sinks, const void *cu_tokens, int total_tokens,
                                        int64_t qkv_token_stride, int window, void *stream);
 
+/* ---- decode, multi-head latent attention (MLA, absorbed form) ------------------- */
+/*
+ * The DeepSeek-V2/V3/R1 and Kimi-K2 family: ONE cache row of 576 elements per token -- a 512-wide latent and a 64-wide
+ * RoPE key -- is shared by all query heads; it is the key over all 576 columns and the value over its first 512.
+ * One new token per sequence, RoPE, cache append and split-KV online softmax fused, as in sfa_decode.
+ * For every sequence b with pos = seq_len[b], 0 <= pos < memory_max_len, and every head h:
+ *   q      = q[b, h, 0:576]                  16-bit; [0:512] = q_nope already absorbed through W_UK, [512:576] = q_pe
+ *   kv     = kv_new[b, 0:576]                16-bit; [0:512] = the (normed) latent c_kv, [512:576] = k_pe
+ *   q[512:576], kv[512:576] = rope(. ; pos)  sfa_decode's recipe: interleaved pairs, rot_dim = 64, fp32 math, rounded to
+ *                                            the 16-bit dtype; angles in-kernel (base 10000) or from rotary_cos/sin_table
+ *                                            [memory_max_len, 32], as sfa_decode takes them (YaRN etc. go through the tables)
+ *   kv_cache[b, idx_layer, pos, :] = kv      the latent 512 copied bit-exact, the rope part as rounded
+ *   o[b, h, 0:512] = softmax(q . C[0..pos]^T * softmax_scale) . C[0..pos][:, 0:512]     C = the cache rows, fp32 accumulate
+ * o is the latent output: the caller applies W_UV.  seq_len is NOT incremented.  softmax_scale <= 0 means 1/sqrt(576);
+ * callers pass the model's own scale.  All operands are 16-bit, fp16 or bf16.
+ * kv_layout: SFA_KV_BLMHD = [batch, num_layer, memory_max_len, 576]; SFA_KV_PAGED = [num_pages, num_layer, page_size,
+ * 576] through block_table, page_size a power of two >= 16.  SFA_KV_BLHMD is rejected (SFA_ERR_BAD_SHAPE): with one kv
+ * head it is the same layout.  num_heads: a multiple of 16 in [16, 128], anything else SFA_ERR_BAD_SHAPE.
+ * sfa_decode's rejection contract holds: an out-of-range seq_len[b], or a bad table entry for the appended page, leaves
+ * the cache untouched, makes o[b] NaN and sets the sticky status word; a bad entry on a page that is only read is not
+ * dereferenced and makes that sequence's outputs NaN.  Cache rows past pos, the other layers and table entries past the
+ * last needed page are never read.  The new row is attended from the call's inputs, never re-read from the cache, and
+ * stored by exactly one workgroup per sequence.  All cache offsets are computed in 64 bits.
+ * Workspace, 256-byte aligned, S = the resolved split count: 256 bytes of status (sfa_decode_reset_status and
+ * sfa_decode_poll_status serve it as they are), then for S > 1 the fp32 partials [batch, num_heads, S, 512] and the
+ * float2 (m, l) [batch, num_heads, S], each rounded up to 256 bytes:
+ *   256 + (S > 1 ? align256(batch * num_heads * S * 2048) + align256(batch * num_heads * S * 8) : 0).
+ * num_splits <= 0: the library's choice (sfa_decode_mla_auto_splits), or the largest count the workspace holds.
+ * Error texts of sfa_last_error() begin with "sfa_decode_mla: ".
+ * Not served: an fp8 latent cache, several new tokens per sequence, head counts that are not multiples of 16 or above
+ * 128, the non-absorbed prefill form, the W_UK / W_UV projections.
+ */
+typedef struct sfa_mla_decode_args {
+    const void *q;                  /* [batch, num_heads, 576]                               */
+    const void *kv_new;             /* [batch, 576]                                          */
+    void *o;                        /* [batch, num_heads, 512]                               */
+    const void *seq_len;            /* int32 [batch]                                         */
+    void *kv_cache;                 /* see above; written at one row per sequence            */
+    const void *rotary_cos_table;   /* [memory_max_len, 32] 16-bit, or NULL:                 */
+    const void *rotary_sin_table;   /*   NULL => cos/sin computed in-kernel in fp32          */
+    const void *block_table;        /* SFA_KV_PAGED: int32 [batch, block_table_stride]       */
+    void *workspace;                /* >= sfa_decode_mla_workspace_bytes(...), 256-B aligned */
+    size_t workspace_bytes;
+    int batch_size;
+    int memory_max_len;
+    int num_heads;
+    int num_layer;
+    int idx_layer;
+    int num_splits;                 /* KV splits; <= 0 => chosen by the library              */
+    int dtype;                      /* sfa_dtype                                             */
+    int kv_layout;                  /* SFA_KV_BLMHD or SFA_KV_PAGED                          */
+    int page_size;                  /* SFA_KV_PAGED: tokens per page, a power of two >= 16   */
+    int block_table_stride;         /* entries per sequence, >= ceil(memory_max_len / page_size) */
+    int num_pages;                  /* pages in the pool (bounds the table entries)          */
+    float softmax_scale;            /* <= 0 => 1/sqrt(576)                                   */
+} sfa_mla_decode_args;
+
+int    sfa_decode_mla(const sfa_mla_decode_args *args, void *stream);
+size_t sfa_decode_mla_workspace_bytes(int batch, int num_heads, int memory_max_len, int num_splits);
+int    sfa_decode_mla_auto_splits(int batch, int num_heads, int memory_max_len);
+
 /* ---- prefill: O = softmax(mask(Q K^T * scale)) V ------------------------------- */
 /*
  * q [batch, heads_q, seqlen_q, head_dim], k/v [batch, heads_kv, seqlen_k, head_dim],

@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = [
     "sfa_prefill_split_fwd", "sfa_prefill_split_workspace_bytes", "sfa_prefill_auto_splits",
     "sfa_prefill_varlen_fwd", "sfa_prefill_varlen_workspace_bytes", "sfa_prefill_varlen_window_fwd",
     "sfa_prefill_varlen_split_fwd", "sfa_prefill_varlen_split_workspace_bytes", "sfa_prefill_varlen_auto_splits",
+    "sfa_decode_mla", "sfa_decode_mla_workspace_bytes", "sfa_decode_mla_auto_splits",
 ]
 
 
@@ -59,6 +60,19 @@ class DecodeArgs(ctypes.Structure):
 
 
 KV_LAYOUTS = {"blmhd": 0, "blhmd": 1, "paged": 2}      # enum sfa_kv_layout
+
+
+class MlaDecodeArgs(ctypes.Structure):
+    """struct sfa_mla_decode_args"""
+    _fields_ = [
+        ("q", ctypes.c_void_p), ("kv_new", ctypes.c_void_p), ("o", ctypes.c_void_p), ("seq_len", ctypes.c_void_p),
+        ("kv_cache", ctypes.c_void_p), ("rotary_cos_table", ctypes.c_void_p), ("rotary_sin_table", ctypes.c_void_p),
+        ("block_table", ctypes.c_void_p), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
+        ("batch_size", ctypes.c_int), ("memory_max_len", ctypes.c_int), ("num_heads", ctypes.c_int),
+        ("num_layer", ctypes.c_int), ("idx_layer", ctypes.c_int), ("num_splits", ctypes.c_int),
+        ("dtype", ctypes.c_int), ("kv_layout", ctypes.c_int), ("page_size", ctypes.c_int),
+        ("block_table_stride", ctypes.c_int), ("num_pages", ctypes.c_int), ("softmax_scale", ctypes.c_float),
+    ]
 
 
 class PrefillArgs(ctypes.Structure):
@@ -137,6 +151,12 @@ def load():
                 fn = getattr(lib, "sfa_decode" + shape + "_window" * window + "_workspace_bytes")
                 fn.restype = ctypes.c_size_t
                 fn.argtypes = [ctypes.c_int] * (6 + bool(shape) + window)
+    lib.sfa_decode_mla.restype = ctypes.c_int
+    lib.sfa_decode_mla.argtypes = [ctypes.POINTER(MlaDecodeArgs), P]
+    lib.sfa_decode_mla_workspace_bytes.restype = ctypes.c_size_t
+    lib.sfa_decode_mla_workspace_bytes.argtypes = [ctypes.c_int] * 4
+    lib.sfa_decode_mla_auto_splits.restype = ctypes.c_int
+    lib.sfa_decode_mla_auto_splits.argtypes = [ctypes.c_int] * 3
     lib.sfa_kv8_quantize.restype = ctypes.c_int
     lib.sfa_kv8_quantize.argtypes = ([ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_int, ctypes.c_int] +
                                      [ctypes.c_int64] * 4 + [ctypes.c_int, ctypes.c_void_p])

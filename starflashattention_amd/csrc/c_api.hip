@@ -708,6 +708,110 @@ int sfa_decode_varlen_kv8_window_sinks(const sfa_decode_args *a, const float *k_
                                                  a->dtype, a->head_dim, (hipStream_t)stream);
 }
 
+// ---- sfa_decode_mla: a family of its own beside the 18 calls above (one latent cache, rows of 576, up to 128 heads) ----
+
+// chunk_auto_splits' shape: the attention kernel runs one 4-wave workgroup per (sequence, block of up to 64 heads, split),
+// one or two per CU: ~256 workgroups, splits of at least 128 cache rows (4 tiles), at most 32.  Measured on MI355X
+// (tools/decode_mla_bench.py --splits): B=4 H=128 at position 4095 takes 347 us unsplit, 69 at 8 splits,
+// 51 at 16 and 47 at 32, so the floor of 512 rows the rule started with was too high; B=64 H=16 is within 8 % of its best
+// (8 splits) at the 4 this picks.
+static int mla_auto_splits(int B, int H, int M) { return clamp_splits((long long)B * ((H + 63) / 64), 256, M, 128); }
+
+static DecodeWorkspace mla_workspace(int B, int H, int S) { return decode_workspace(0, 0, (size_t)B * H, S, 512); }
+
+int sfa_decode_mla_auto_splits(int batch, int num_heads, int memory_max_len) {
+    if (batch <= 0 || num_heads <= 0 || memory_max_len <= 0) return 1;
+    return mla_auto_splits(batch, num_heads, memory_max_len);
+}
+
+size_t sfa_decode_mla_workspace_bytes(int batch, int num_heads, int memory_max_len, int num_splits) {
+    if (batch <= 0 || num_heads <= 0) return kStatusBytes;
+    const int S = num_splits > 0 ? num_splits : sfa_decode_mla_auto_splits(batch, num_heads, memory_max_len);
+    return mla_workspace(batch, num_heads, S).total;
+}
+
+// The order of the checks follows the decode host pipeline: NULL pointers, dtype, shape, layout and paging fields, then
+// the workspace's alignment and size.
+int sfa_decode_mla(const sfa_mla_decode_args *a, void *stream) {
+    const char *fn = "sfa_decode_mla";
+    if (!a) return fail(SFA_ERR_NULL_POINTER, "%s: args is NULL", fn);
+    if (!a->q || !a->kv_new || !a->o || !a->seq_len || !a->kv_cache)
+        return fail(SFA_ERR_NULL_POINTER, "%s: q/kv_new/o/seq_len/kv_cache must be non-NULL", fn);
+    if ((a->rotary_cos_table == nullptr) != (a->rotary_sin_table == nullptr))
+        return fail(SFA_ERR_NULL_POINTER, "%s: give both rotary tables or neither", fn);
+    if (!a->workspace) return fail(SFA_ERR_NULL_POINTER, "%s: workspace is NULL", fn);
+    if (a->dtype != SFA_DTYPE_FP16 && a->dtype != SFA_DTYPE_BF16)
+        return fail(SFA_ERR_BAD_DTYPE, "%s: dtype %d is not fp16(0)/bf16(1)", fn, a->dtype);
+    if (a->batch_size < 0 || a->batch_size > 65535 || a->memory_max_len <= 0 || a->num_layer <= 0)
+        return fail(SFA_ERR_BAD_SHAPE, "%s: batch_size=%d (<= 65535) memory_max_len=%d num_layer=%d", fn, a->batch_size,
+                    a->memory_max_len, a->num_layer);
+    if (a->num_heads < 16 || a->num_heads > 128 || a->num_heads % 16)
+        return fail(SFA_ERR_BAD_SHAPE, "%s: num_heads=%d must be a multiple of 16 in [16, 128]", fn, a->num_heads);
+    if (a->idx_layer < 0 || a->idx_layer >= a->num_layer)
+        return fail(SFA_ERR_BAD_SHAPE, "%s: idx_layer=%d outside [0, num_layer=%d)", fn, a->idx_layer, a->num_layer);
+    if (a->num_splits > 1024) return fail(SFA_ERR_BAD_SHAPE, "%s: num_splits=%d > 1024", fn, a->num_splits);
+    if (a->kv_layout != SFA_KV_BLMHD && a->kv_layout != SFA_KV_PAGED)
+        return fail(SFA_ERR_BAD_SHAPE,
+                    "%s: kv_layout %d is not SFA_KV_BLMHD(0)/SFA_KV_PAGED(2) (with one kv head SFA_KV_BLHMD is SFA_KV_BLMHD)",
+                    fn, a->kv_layout);
+    int page_shift = 0;
+    if (a->kv_layout == SFA_KV_PAGED) {
+        if (!a->block_table) return fail(SFA_ERR_NULL_POINTER, "%s: kv_layout PAGED needs block_table", fn);
+        if (a->page_size < 16 || (a->page_size & (a->page_size - 1)))
+            return fail(SFA_ERR_BAD_SHAPE, "%s: page_size=%d must be a power of two >= 16", fn, a->page_size);
+        while ((1 << page_shift) < a->page_size) ++page_shift;
+        if (a->num_pages <= 0 || (long long)a->block_table_stride * a->page_size < (long long)a->memory_max_len)
+            return fail(SFA_ERR_BAD_SHAPE,
+                        "%s: num_pages=%d, block_table_stride=%d * page_size=%d must cover memory_max_len=%d", fn,
+                        a->num_pages, a->block_table_stride, a->page_size, a->memory_max_len);
+        if ((uintptr_t)a->block_table & 3) return fail(SFA_ERR_BAD_SHAPE, "%s: block_table must be 4-byte aligned", fn);
+    }
+    if (((uintptr_t)a->q | (uintptr_t)a->kv_new | (uintptr_t)a->o | (uintptr_t)a->kv_cache) & 15)
+        return fail(SFA_ERR_BAD_SHAPE, "%s: tensors must be 16-byte aligned", fn);
+    if ((uintptr_t)a->workspace & 255) return fail(SFA_ERR_BAD_SHAPE, "%s: workspace must be 256-byte aligned", fn);
+    const int B = a->batch_size, H = a->num_heads;
+    int S = a->num_splits > 0 ? a->num_splits : mla_auto_splits(B, H, a->memory_max_len);
+    // a caller that left the choice to the library gets the largest split count its workspace holds, as in sfa_decode
+    if (a->num_splits <= 0)
+        while (S > 1 && a->workspace_bytes < mla_workspace(B, H, S).total) --S;
+    const DecodeWorkspace w = mla_workspace(B, H, S);
+    if (a->workspace_bytes < w.total)
+        return fail(SFA_ERR_WORKSPACE_TOO_SMALL, "%s: workspace has %zu bytes, need %zu", fn, a->workspace_bytes, w.total);
+    if (B == 0) return SFA_OK;
+
+    MlaKernelParams mp;
+    memset(&mp, 0, sizeof(mp));
+    DecodeKernelParams &p = mp.d;
+    p.qkv = (const uint16_t *)a->q;
+    p.o = (uint16_t *)a->o;
+    p.seq_len = (const int32_t *)a->seq_len;
+    p.k_cache = (uint16_t *)a->kv_cache;
+    p.cos_tab = (const uint16_t *)a->rotary_cos_table;
+    p.sin_tab = (const uint16_t *)a->rotary_sin_table;
+    char *ws = (char *)a->workspace;
+    p.status = (int32_t *)ws;
+    p.part_o = (float *)(ws + w.part_o);
+    p.part_ml = (float2 *)(ws + w.part_ml);
+    p.B = B, p.M = a->memory_max_len, p.H = H, p.Hkv = 1, p.L = a->num_layer, p.layer = a->idx_layer;
+    p.rot_dim = 64;
+    p.num_splits = S;
+    p.qkv_stride = (long long)H * 576;
+    p.kv_row_stride = 576;
+    p.kv_head_stride = 576;
+    if (a->kv_layout == SFA_KV_PAGED) {
+        p.block_table = (const int32_t *)a->block_table;
+        p.page_shift = page_shift;
+        p.table_stride = a->block_table_stride;
+        p.num_pages = a->num_pages;
+        p.page_stride = (long long)a->num_layer * a->page_size * 576;
+    }
+    const float scale = a->softmax_scale > 0.f ? a->softmax_scale : 1.0f / std::sqrt(576.0f);
+    p.scale_log2 = scale * 1.4426950408889634f;
+    mp.kv_new = (const uint16_t *)a->kv_new;
+    mp.kv_new_stride = 576;
+    return launch_mla_decode(mp, a->dtype, (hipStream_t)stream);
+}
+
 int sfa_kv8_quantize(void *dst, const void *src, const float *scale, int64_t rows, int num_heads_kv, int head_dim,
                      int64_t src_row_stride, int64_t src_head_stride, int64_t dst_row_stride, int64_t dst_head_stride,
                      int dtype, void *stream) {

@@ -171,6 +171,19 @@ struct VarlenKv8WindowSinksKernelParams {
     const float *sinks;
 };
 
+// sfa_decode_mla (decode_mla_kernel.hip): latent attention over ONE cache of 576-element rows, key over all 576
+// columns and value over the first 512.  Workspace, for S = the resolved num_splits:
+//   [0, 256)   status block
+//   part_o     (S > 1) fp32 [B, H, S, 512], rounded up to 256 bytes
+//   part_ml    (S > 1) float2 [B, H, S], rounded up to 256 bytes
+// = decode_workspace(0, 0, B * H, S, 512): 256 + (S > 1 ? align256(B*H*S*2048) + align256(B*H*S*8) : 0) bytes.
+struct MlaKernelParams {
+    DecodeKernelParams d;   // qkv = q [B, H, 576] (qkv_stride = H * 576), o = [B, H, 512], k_cache = the latent cache
+                            // (v_cache unused), Hkv = 1, rot_dim = 64, kv_row_stride = 576; the rest as in sfa_decode
+    const uint16_t *kv_new; // [B, 576]
+    long long kv_new_stride;    // elements between batches of kv_new
+};
+
 struct PrefillKernelParams {
     const uint16_t *q, *k, *v;
     uint16_t *o;
@@ -282,6 +295,9 @@ int launch_decode_chunk_kv8_window_sinks(const ChunkKv8WindowSinksKernelParams &
                                          hipStream_t stream);
 int launch_decode_varlen_kv8_window_sinks(const VarlenKv8WindowSinksKernelParams &p, int dtype, int head_dim,
                                           hipStream_t stream);
+// decode_mla_kernel.hip: called by sfa_decode_mla only (validated dtype, num_heads a multiple of 16 in [16, 128]): the
+// attention kernel, then (two or more splits) the combine, on the same stream
+int launch_mla_decode(const MlaKernelParams &p, int dtype, hipStream_t stream);
 int launch_prefill(const PrefillKernelParams &p, int dtype, int head_dim, bool causal, hipStream_t stream);
 int launch_prefill_no_keys(const PrefillKernelParams &p, int head_dim, hipStream_t stream);
 // prefill_window_kernel.hip: called by sfa_prefill_window_fwd only (validated dtype, head_dim 64 / 128, Sk > 0)

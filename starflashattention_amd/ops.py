@@ -566,6 +566,73 @@ def flash_decode_varlen_kv8_window_sinks(qkv, q_bias, k_bias, v_bias, k_cache_ta
                       cu_tokens=cu_tokens, window=window, sinks=sinks, k_scale=k_scale, v_scale=v_scale)
 
 
+MLA_DIM, MLA_LATENT = 576, 512      # a latent-attention cache row (the key), and its first columns (the value)
+
+
+def decode_mla_auto_splits(batch, num_heads, memory_max_len):
+    """The split count flash_decode_mla picks at num_splits=0 (sfa_decode_mla_auto_splits)."""
+    return int(_lib.load().sfa_decode_mla_auto_splits(int(batch), int(num_heads), int(memory_max_len)))
+
+
+def decode_mla_workspace_bytes(batch, num_heads, memory_max_len, num_splits=0):
+    """Bytes of scratch flash_decode_mla needs (sfa_decode_mla_workspace_bytes); num_splits=0: the library's choice."""
+    return int(_lib.load().sfa_decode_mla_workspace_bytes(int(batch), int(num_heads), int(memory_max_len),
+                                                          int(num_splits)))
+
+
+def flash_decode_mla(q, kv_new, kv_cache, seq_len, o, *, idx_layer, softmax_scale=None, num_splits=0,
+                     rotary_cos_table=None, rotary_sin_table=None, block_table=None, page_size=0):
+    """One decode step of multi-head latent attention in absorbed form (include/star_flash_attn.h, sfa_decode_mla).
+    q [B, H, 576] (512 absorbed no-rope dims, then 64 rope dims), kv_new [B, 576] (latent, then the rope key),
+    o [B, H, 512] (the latent output: the caller applies W_UV), seq_len int32 [B].  kv_cache: [B, L, M, 576], or with
+    block_table (int32 [B, pages_per_seq]) the pool [num_pages, L, page_size, 576]; memory_max_len is then
+    pages_per_seq * page_size.  H: a multiple of 16 in [16, 128].  softmax_scale None: 1/sqrt(576) -- pass the model's
+    own.  rotary tables: [memory_max_len, 32] of q's dtype, or None for in-kernel angles.  Returns `o`."""
+    lib = _lib.load()
+    _require(isinstance(q, torch.Tensor) and q.dtype in _DTYPES and q.dim() == 3,
+             f"q must be a float16 or bfloat16 [B, H, {MLA_DIM}] tensor")
+    dt, dev = q.dtype, q.device
+    B, H = int(q.shape[0]), int(q.shape[1])
+    _check_gpu_tensor(q, "q", dt, (B, H, MLA_DIM))
+    _check_gpu_tensor(kv_new, "kv_new", dt, (B, MLA_DIM), dev)
+    _check_gpu_tensor(o, "o", dt, (B, H, MLA_LATENT), dev)
+    _check_gpu_tensor(seq_len, "seq_len", torch.int32, (B,), dev)
+    _require(isinstance(kv_cache, torch.Tensor) and kv_cache.dim() == 4,
+             f"kv_cache must be [B, L, M, {MLA_DIM}], or with block_table [num_pages, L, page_size, {MLA_DIM}]")
+    L = int(kv_cache.shape[1])
+    a = _lib.MlaDecodeArgs()
+    if block_table is not None:
+        num_pages, P = int(kv_cache.shape[0]), int(kv_cache.shape[2])
+        _require(page_size in (0, P), f"page_size={page_size} does not match the pool's {P} rows per page")
+        _require(isinstance(block_table, torch.Tensor) and block_table.dim() == 2, "block_table must be int32 [B, pages_per_seq]")
+        _check_gpu_tensor(block_table, "block_table", torch.int32, (B, int(block_table.shape[1])), dev)
+        _check_gpu_tensor(kv_cache, "kv_cache", dt, (num_pages, L, P, MLA_DIM), dev)
+        M = int(block_table.shape[1]) * P
+        a.kv_layout, a.page_size, a.num_pages = _lib.KV_LAYOUTS["paged"], P, num_pages
+        a.block_table, a.block_table_stride = block_table.data_ptr(), int(block_table.shape[1])
+    else:
+        M = int(kv_cache.shape[2])
+        _check_gpu_tensor(kv_cache, "kv_cache", dt, (B, L, M, MLA_DIM), dev)
+        a.kv_layout = _lib.KV_LAYOUTS["blmhd"]
+    for name, t in (("rotary_cos_table", rotary_cos_table), ("rotary_sin_table", rotary_sin_table)):
+        if t is not None:
+            _check_gpu_tensor(t, name, dt, (M, 32), dev)
+    a.q, a.kv_new, a.o, a.seq_len, a.kv_cache = (t.data_ptr() for t in (q, kv_new, o, seq_len, kv_cache))
+    a.rotary_cos_table = rotary_cos_table.data_ptr() if rotary_cos_table is not None else None
+    a.rotary_sin_table = rotary_sin_table.data_ptr() if rotary_sin_table is not None else None
+    a.batch_size, a.memory_max_len, a.num_heads, a.num_layer, a.idx_layer = B, M, H, L, int(idx_layer)
+    a.dtype = _DTYPES[dt]
+    a.softmax_scale = float(softmax_scale) if softmax_scale else 0.0
+    with torch.cuda.device(dev):
+        S = int(num_splits) if num_splits and num_splits > 0 else lib.sfa_decode_mla_auto_splits(B, H, M)
+        ws = _workspace(dev, lib.sfa_decode_mla_workspace_bytes(B, H, M, S))
+        a.num_splits, a.workspace, a.workspace_bytes = S, ws.data_ptr(), ws.numel()
+        _lib.check(lib.sfa_decode_mla(ctypes.byref(a), _stream_ptr(dev)))
+        if _sync_checks:
+            check_decode_status(dev)
+    return o
+
+
 def check_decode_status(device=None):
     """Synchronise the current stream and raise if any decode call on it saw a bad seq_len."""
     lib = _lib.load()
