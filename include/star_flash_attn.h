@@ -599,8 +599,9 @@ int sfa_decode_varlen_kv8_window_sinks(const sfa_decode_args *args, const float 
  *   256 + (S > 1 ? align256(batch * num_heads * S * 2048) + align256(batch * num_heads * S * 8) : 0).
  * num_splits <= 0: the library's choice (sfa_decode_mla_auto_splits), or the largest count the workspace holds.
  * Error texts of sfa_last_error() begin with "sfa_decode_mla: ".
- * Not served: an fp8 latent cache, several new tokens per sequence, head counts that are not multiples of 16 or above
- * 128, the non-absorbed prefill form, the W_UK / W_UV projections.
+ * Not served: an fp8 latent cache, a ragged batch of new tokens (sfa_decode_mla_chunk takes the same count for every
+ * sequence), head counts that are not multiples of 16 or above 128, the non-absorbed prefill form, the W_UK / W_UV
+ * projections.
  */
 typedef struct sfa_mla_decode_args {
     const void *q;                  /* [batch, num_heads, 576]                               */
@@ -630,6 +631,33 @@ typedef struct sfa_mla_decode_args {
 int    sfa_decode_mla(const sfa_mla_decode_args *args, void *stream);
 size_t sfa_decode_mla_workspace_bytes(int batch, int num_heads, int memory_max_len, int num_splits);
 int    sfa_decode_mla_auto_splits(int batch, int num_heads, int memory_max_len);
+
+/*
+ * sfa_decode_mla_chunk: num_tokens = n new tokens per sequence in one pass over the cache -- the multi-token-prediction
+ * head of DeepSeek-V3, speculative verification, the tail of a chunked prompt.  The call is exactly n successive
+ * sfa_decode_mla calls with seq_len[b] advanced by one between them.  For pos = seq_len[b] and t in [0, n):
+ *   q[b, t, h, 0:576] and kv_new[b, t, 0:576] are roped at position pos + t (recipe, tables and rounding as above)
+ *   kv_cache[b, idx_layer, pos + t, :] = kv_new[b, t]       the latent bit-exact, the rope part as rounded
+ *   o[b, t, h, 0:512] = softmax(q . C[0..pos+t]^T * softmax_scale) . C[0..pos+t][:, 0:512]
+ * so token t sees the history and the new tokens 0..t.  q [batch, n, num_heads, 576], kv_new [batch, n, 576] and
+ * o [batch, n, num_heads, 512] are contiguous; every other field of sfa_mla_decode_args keeps its meaning, and
+ * num_heads, layouts, dtypes and softmax_scale are sfa_decode_mla's.  seq_len is NOT incremented.
+ * 1 <= num_tokens <= 32; 0 does nothing and returns SFA_OK; anything else is SFA_ERR_BAD_SHAPE.
+ * Rejection is sfa_decode_chunk's rule: pos < 0, pos + n > memory_max_len, or (paged) a bad table entry of a page
+ * covering [pos, pos + n) leaves the sequence's cache untouched, makes all n * num_heads rows of o[b] NaN and sets the
+ * sticky status word; a bad entry on a page that is only read is not dereferenced and makes that sequence's outputs
+ * NaN.  Rows at and above pos + n, the other layers and table entries past the last needed page are never read.  The
+ * new rows are attended from the call's inputs, never re-read from the cache, and stored by exactly one workgroup per
+ * sequence.
+ * Workspace, 256-byte aligned, S = the resolved split count: 256 bytes of status, then for S > 1 the fp32 partials
+ * [batch, n, num_heads, S, 512] and the float2 (m, l) [batch, n, num_heads, S], each rounded up to 256 bytes:
+ *   256 + (S > 1 ? align256(batch * n * num_heads * S * 2048) + align256(batch * n * num_heads * S * 8) : 0).
+ * num_splits <= 0: the library's choice (sfa_decode_mla_chunk_auto_splits), or the largest count the workspace holds.
+ * Error texts of sfa_last_error() begin with "sfa_decode_mla_chunk: ".
+ */
+int    sfa_decode_mla_chunk(const sfa_mla_decode_args *args, int num_tokens, void *stream);
+size_t sfa_decode_mla_chunk_workspace_bytes(int batch, int num_heads, int memory_max_len, int num_tokens, int num_splits);
+int    sfa_decode_mla_chunk_auto_splits(int batch, int num_heads, int memory_max_len, int num_tokens);
 
 /* ---- prefill: O = softmax(mask(Q K^T * scale)) V ------------------------------- */
 /*

@@ -14,6 +14,7 @@ from .ops import (  # noqa: F401
     flash_attn_varlen_fwd, prefill_varlen_workspace_bytes, flash_attn_varlen_window_fwd,
     flash_attn_varlen_split_fwd, prefill_varlen_auto_splits, prefill_varlen_split_workspace_bytes,
     flash_decode_mla, decode_mla_auto_splits, decode_mla_workspace_bytes,
+    flash_decode_mla_chunk, decode_mla_chunk_auto_splits, decode_mla_chunk_workspace_bytes,
     compute_rotary_table, fill_16bit, check_decode_status, set_sync_checks, release_workspaces,
 )
 from ._lib import SfaError, LIB_PATH, debug_set, debug_get, last_prefill_kernel  # noqa: F401

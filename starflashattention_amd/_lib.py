@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = [
     "sfa_prefill_varlen_fwd", "sfa_prefill_varlen_workspace_bytes", "sfa_prefill_varlen_window_fwd",
     "sfa_prefill_varlen_split_fwd", "sfa_prefill_varlen_split_workspace_bytes", "sfa_prefill_varlen_auto_splits",
     "sfa_decode_mla", "sfa_decode_mla_workspace_bytes", "sfa_decode_mla_auto_splits",
+    "sfa_decode_mla_chunk", "sfa_decode_mla_chunk_workspace_bytes", "sfa_decode_mla_chunk_auto_splits",
 ]
 
 
@@ -157,6 +158,12 @@ def load():
     lib.sfa_decode_mla_workspace_bytes.argtypes = [ctypes.c_int] * 4
     lib.sfa_decode_mla_auto_splits.restype = ctypes.c_int
     lib.sfa_decode_mla_auto_splits.argtypes = [ctypes.c_int] * 3
+    lib.sfa_decode_mla_chunk.restype = ctypes.c_int
+    lib.sfa_decode_mla_chunk.argtypes = [ctypes.POINTER(MlaDecodeArgs), ctypes.c_int, P]
+    lib.sfa_decode_mla_chunk_workspace_bytes.restype = ctypes.c_size_t
+    lib.sfa_decode_mla_chunk_workspace_bytes.argtypes = [ctypes.c_int] * 5
+    lib.sfa_decode_mla_chunk_auto_splits.restype = ctypes.c_int
+    lib.sfa_decode_mla_chunk_auto_splits.argtypes = [ctypes.c_int] * 4
     lib.sfa_kv8_quantize.restype = ctypes.c_int
     lib.sfa_kv8_quantize.argtypes = ([ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_int, ctypes.c_int] +
                                      [ctypes.c_int64] * 4 + [ctypes.c_int, ctypes.c_void_p])

@@ -23,8 +23,9 @@ OBJDIR = os.path.join(ROOT, "build", "obj")
 LIB_NAME = "libStarFlashAttention.so"
 ARCH = "gfx950"
 
-# per-source extra hipcc flags (decode_mla_kernel.hip: no packed fp32 VALU instructions)
-EXTRA_FLAGS = {"decode_mla_kernel.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+# per-source extra hipcc flags (the latent-attention kernels: no packed fp32 VALU instructions)
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+EXTRA_FLAGS = {"decode_mla_kernel.hip": _NO_PK_F32, "decode_mla_chunk_kernel.hip": _NO_PK_F32}
 
 # (the longest compiles first: the pool below takes the sources in this order)
 KERNEL_SOURCES = ["prefill_w4_kernel.hip", "prefill_w4_kernel_p1.hip", "prefill_w4_kernel_p2.hip", "prefill_w4_kernel_p3.hip",
@@ -34,7 +35,7 @@ KERNEL_SOURCES = ["prefill_w4_kernel.hip", "prefill_w4_kernel_p1.hip", "prefill_
                   "decode_chunk_kv8_window_kernel.hip", "decode_varlen_kv8_window_kernel.hip",
                   "decode_chunk_window_sinks_kernel.hip", "decode_varlen_window_sinks_kernel.hip",
                   "decode_chunk_kv8_window_sinks_kernel.hip", "decode_varlen_kv8_window_sinks_kernel.hip",
-                  "decode_window_sinks_kernel.hip", "decode_kv8_window_sinks_kernel.hip", "decode_mla_kernel.hip", "decode_kernel.hip", "decode_gqa_kernel.hip", "decode_gqa_mfma_kernel.hip", "decode_kv8_kernel.hip", "decode_kv8_window_kernel.hip", "decode_window_kernel.hip",
+                  "decode_window_sinks_kernel.hip", "decode_kv8_window_sinks_kernel.hip", "decode_mla_kernel.hip", "decode_mla_chunk_kernel.hip", "decode_kernel.hip", "decode_gqa_kernel.hip", "decode_gqa_mfma_kernel.hip", "decode_kv8_kernel.hip", "decode_kv8_window_kernel.hip", "decode_window_kernel.hip",
                   "prefill_d256_kernel.hip",
                   "prefill_kernel.hip", "prefill_kernel_bm128.hip", "prefill_window_kernel.hip", "prefill_split_kernel.hip", "prefill_varlen_kernel.hip", "prefill_varlen_window_kernel.hip", "prefill_varlen_split_kernel.hip", "prefill_dispatch.hip", "decode_dispatch.hip",
                   "aux_kernels.hip", "c_api.hip", "cxx_surface.hip"]

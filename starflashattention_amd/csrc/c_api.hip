@@ -717,7 +717,16 @@ int sfa_decode_varlen_kv8_window_sinks(const sfa_decode_args *a, const float *k_
 // (8 splits) at the 4 this picks.
 static int mla_auto_splits(int B, int H, int M) { return clamp_splits((long long)B * ((H + 63) / 64), 256, M, 128); }
 
-static DecodeWorkspace mla_workspace(int B, int H, int S) { return decode_workspace(0, 0, (size_t)B * H, S, 512); }
+// sfa_decode_mla_chunk: the grid's x extent is the number of groups of row blocks (sfa_host.h), so the same rule counts
+// B * groups workgroups.  Measured on MI355X (tools/decode_mla_chunk_bench.py --splits), the rule's pick
+// is the best of 1 .. 32 on both lines swept: B=64 H=16 n=4 at position 4095 takes 360 us unsplit, 125 at the 4 splits it
+// picks, 146 at 8; B=4 H=128 n=2 takes 354 unsplit, 69 at 8, 50 at the 16 it picks, 71 at 32.
+static int mla_chunk_auto_splits(int B, int H, int M, int n) {
+    return clamp_splits((long long)B * mla_chunk_groups(n * (H / 16)), 256, M, 128);
+}
+
+// rows = query rows per sequence: num_heads, times num_tokens for the chunk
+static DecodeWorkspace mla_workspace(int B, int rows, int S) { return decode_workspace(0, 0, (size_t)B * rows, S, 512); }
 
 int sfa_decode_mla_auto_splits(int batch, int num_heads, int memory_max_len) {
     if (batch <= 0 || num_heads <= 0 || memory_max_len <= 0) return 1;
@@ -730,10 +739,23 @@ size_t sfa_decode_mla_workspace_bytes(int batch, int num_heads, int memory_max_l
     return mla_workspace(batch, num_heads, S).total;
 }
 
-// The order of the checks follows the decode host pipeline: NULL pointers, dtype, shape, layout and paging fields, then
-// the workspace's alignment and size.
-int sfa_decode_mla(const sfa_mla_decode_args *a, void *stream) {
-    const char *fn = "sfa_decode_mla";
+int sfa_decode_mla_chunk_auto_splits(int batch, int num_heads, int memory_max_len, int num_tokens) {
+    if (batch <= 0 || num_heads <= 0 || memory_max_len <= 0 || num_tokens <= 0) return 1;
+    return mla_chunk_auto_splits(batch, num_heads, memory_max_len, num_tokens);
+}
+
+size_t sfa_decode_mla_chunk_workspace_bytes(int batch, int num_heads, int memory_max_len, int num_tokens, int num_splits) {
+    if (batch <= 0 || num_heads <= 0 || num_tokens <= 0) return kStatusBytes;
+    const int S = num_splits > 0 ? num_splits
+                                 : sfa_decode_mla_chunk_auto_splits(batch, num_heads, memory_max_len, num_tokens);
+    return mla_workspace(batch, num_heads * num_tokens, S).total;
+}
+
+// What sfa_decode_mla (chunk = false, n = 1) and sfa_decode_mla_chunk (n = num_tokens) check and marshal alike, under the
+// name of the call.  The order of the checks follows the decode host pipeline: NULL pointers, dtype, shape, layout and
+// paging fields, then the workspace's alignment and size.  Returns kRun with *out filled (the batch strides of q and kv_new for n
+// contiguous tokens), SFA_OK where there is nothing to do (batch_size or n of 0), or an error.
+static int mla_call(const char *fn, const sfa_mla_decode_args *a, bool chunk, int n, MlaKernelParams *out) {
     if (!a) return fail(SFA_ERR_NULL_POINTER, "%s: args is NULL", fn);
     if (!a->q || !a->kv_new || !a->o || !a->seq_len || !a->kv_cache)
         return fail(SFA_ERR_NULL_POINTER, "%s: q/kv_new/o/seq_len/kv_cache must be non-NULL", fn);
@@ -747,6 +769,7 @@ int sfa_decode_mla(const sfa_mla_decode_args *a, void *stream) {
                     a->memory_max_len, a->num_layer);
     if (a->num_heads < 16 || a->num_heads > 128 || a->num_heads % 16)
         return fail(SFA_ERR_BAD_SHAPE, "%s: num_heads=%d must be a multiple of 16 in [16, 128]", fn, a->num_heads);
+    if (n < 0 || n > 32) return fail(SFA_ERR_BAD_SHAPE, "%s: num_tokens=%d outside [0, 32]", fn, n);
     if (a->idx_layer < 0 || a->idx_layer >= a->num_layer)
         return fail(SFA_ERR_BAD_SHAPE, "%s: idx_layer=%d outside [0, num_layer=%d)", fn, a->idx_layer, a->num_layer);
     if (a->num_splits > 1024) return fail(SFA_ERR_BAD_SHAPE, "%s: num_splits=%d > 1024", fn, a->num_splits);
@@ -770,16 +793,18 @@ int sfa_decode_mla(const sfa_mla_decode_args *a, void *stream) {
         return fail(SFA_ERR_BAD_SHAPE, "%s: tensors must be 16-byte aligned", fn);
     if ((uintptr_t)a->workspace & 255) return fail(SFA_ERR_BAD_SHAPE, "%s: workspace must be 256-byte aligned", fn);
     const int B = a->batch_size, H = a->num_heads;
-    int S = a->num_splits > 0 ? a->num_splits : mla_auto_splits(B, H, a->memory_max_len);
+    int S = a->num_splits > 0 ? a->num_splits
+            : chunk ? (n > 0 ? mla_chunk_auto_splits(B, H, a->memory_max_len, n) : 1)
+                    : mla_auto_splits(B, H, a->memory_max_len);
     // a caller that left the choice to the library gets the largest split count its workspace holds, as in sfa_decode
     if (a->num_splits <= 0)
-        while (S > 1 && a->workspace_bytes < mla_workspace(B, H, S).total) --S;
-    const DecodeWorkspace w = mla_workspace(B, H, S);
+        while (S > 1 && a->workspace_bytes < mla_workspace(B, H * n, S).total) --S;
+    const DecodeWorkspace w = mla_workspace(B, H * n, S);
     if (a->workspace_bytes < w.total)
         return fail(SFA_ERR_WORKSPACE_TOO_SMALL, "%s: workspace has %zu bytes, need %zu", fn, a->workspace_bytes, w.total);
-    if (B == 0) return SFA_OK;
+    if (B == 0 || n == 0) return SFA_OK;
 
-    MlaKernelParams mp;
+    MlaKernelParams &mp = *out;
     memset(&mp, 0, sizeof(mp));
     DecodeKernelParams &p = mp.d;
     p.qkv = (const uint16_t *)a->q;
@@ -795,7 +820,7 @@ int sfa_decode_mla(const sfa_mla_decode_args *a, void *stream) {
     p.B = B, p.M = a->memory_max_len, p.H = H, p.Hkv = 1, p.L = a->num_layer, p.layer = a->idx_layer;
     p.rot_dim = 64;
     p.num_splits = S;
-    p.qkv_stride = (long long)H * 576;
+    p.qkv_stride = (long long)n * H * 576;
     p.kv_row_stride = 576;
     p.kv_head_stride = 576;
     if (a->kv_layout == SFA_KV_PAGED) {
@@ -808,9 +833,26 @@ int sfa_decode_mla(const sfa_mla_decode_args *a, void *stream) {
     const float scale = a->softmax_scale > 0.f ? a->softmax_scale : 1.0f / std::sqrt(576.0f);
     p.scale_log2 = scale * 1.4426950408889634f;
     mp.kv_new = (const uint16_t *)a->kv_new;
-    mp.kv_new_stride = 576;
+    mp.kv_new_stride = (long long)n * 576;
+    return kRun;
+}
+
+int sfa_decode_mla(const sfa_mla_decode_args *a, void *stream) {
+    MlaKernelParams mp;
+    if (const int rc = mla_call("sfa_decode_mla", a, false, 1, &mp); rc != kRun) return rc;
     return launch_mla_decode(mp, a->dtype, (hipStream_t)stream);
 }
+
+int sfa_decode_mla_chunk(const sfa_mla_decode_args *a, int num_tokens, void *stream) {
+    MlaChunkKernelParams cp;
+    if (const int rc = mla_call("sfa_decode_mla_chunk", a, true, num_tokens, &cp.m); rc != kRun) return rc;
+    cp.n = num_tokens;
+    cp.q_tok_stride = (long long)a->num_heads * 576;
+    cp.kv_tok_stride = 576;
+    cp.o_tok_stride = (long long)a->num_heads * 512;
+    return launch_mla_decode_chunk(cp, a->dtype, (hipStream_t)stream);
+}
+
 
 int sfa_kv8_quantize(void *dst, const void *src, const float *scale, int64_t rows, int num_heads_kv, int head_dim,
                      int64_t src_row_stride, int64_t src_head_stride, int64_t dst_row_stride, int64_t dst_head_stride,

@@ -184,6 +184,16 @@ struct MlaKernelParams {
     long long kv_new_stride;    // elements between batches of kv_new
 };
 
+// sfa_decode_mla_chunk (decode_mla_chunk_kernel.hip): n new tokens per sequence over the same cache.  A query row is
+// (b, t, h); its partials sit at row (b * n + t) * H + h of sfa_decode_mla's workspace layout with B * n * H rows:
+// decode_workspace(0, 0, B * n * H, S, 512).
+struct MlaChunkKernelParams {
+    MlaKernelParams m;      // d.qkv = q [B, n, H, 576] (qkv_stride = n * q_tok_stride), d.o = [B, n, H, 512],
+                            // kv_new = [B, n, 576] (kv_new_stride = n * kv_tok_stride); the rest as in sfa_decode_mla
+    int n;                  // new tokens per sequence, 1 .. 32 (one key tile)
+    long long q_tok_stride, kv_tok_stride, o_tok_stride;    // elements between the tokens of a sequence
+};
+
 struct PrefillKernelParams {
     const uint16_t *q, *k, *v;
     uint16_t *o;
@@ -298,6 +308,11 @@ int launch_decode_varlen_kv8_window_sinks(const VarlenKv8WindowSinksKernelParams
 // decode_mla_kernel.hip: called by sfa_decode_mla only (validated dtype, num_heads a multiple of 16 in [16, 128]): the
 // attention kernel, then (two or more splits) the combine, on the same stream
 int launch_mla_decode(const MlaKernelParams &p, int dtype, hipStream_t stream);
+// decode_mla_chunk_kernel.hip: called by sfa_decode_mla_chunk only (the same validation, 1 <= n <= 32): the attention
+// kernel over the n * num_heads / 16 row blocks, then (two or more splits) the combine, on the same stream
+int launch_mla_decode_chunk(const MlaChunkKernelParams &p, int dtype, hipStream_t stream);
+// workgroups per (split, sequence) of that attention kernel for R = n * num_heads / 16 row blocks: the grid's x extent
+inline int mla_chunk_groups(int R) { return R <= 2 ? 1 : (R + 3) / 4; }
 int launch_prefill(const PrefillKernelParams &p, int dtype, int head_dim, bool causal, hipStream_t stream);
 int launch_prefill_no_keys(const PrefillKernelParams &p, int head_dim, hipStream_t stream);
 // prefill_window_kernel.hip: called by sfa_prefill_window_fwd only (validated dtype, head_dim 64 / 128, Sk > 0)

@@ -580,22 +580,31 @@ def decode_mla_workspace_bytes(batch, num_heads, memory_max_len, num_splits=0):
                                                           int(num_splits)))
 
 
-def flash_decode_mla(q, kv_new, kv_cache, seq_len, o, *, idx_layer, softmax_scale=None, num_splits=0,
-                     rotary_cos_table=None, rotary_sin_table=None, block_table=None, page_size=0):
-    """One decode step of multi-head latent attention in absorbed form (include/star_flash_attn.h, sfa_decode_mla).
-    q [B, H, 576] (512 absorbed no-rope dims, then 64 rope dims), kv_new [B, 576] (latent, then the rope key),
-    o [B, H, 512] (the latent output: the caller applies W_UV), seq_len int32 [B].  kv_cache: [B, L, M, 576], or with
-    block_table (int32 [B, pages_per_seq]) the pool [num_pages, L, page_size, 576]; memory_max_len is then
-    pages_per_seq * page_size.  H: a multiple of 16 in [16, 128].  softmax_scale None: 1/sqrt(576) -- pass the model's
-    own.  rotary tables: [memory_max_len, 32] of q's dtype, or None for in-kernel angles.  Returns `o`."""
-    lib = _lib.load()
-    _require(isinstance(q, torch.Tensor) and q.dtype in _DTYPES and q.dim() == 3,
-             f"q must be a float16 or bfloat16 [B, H, {MLA_DIM}] tensor")
+def decode_mla_chunk_auto_splits(batch, num_heads, memory_max_len, num_tokens):
+    """The split count flash_decode_mla_chunk picks at num_splits=0 (sfa_decode_mla_chunk_auto_splits)."""
+    return int(_lib.load().sfa_decode_mla_chunk_auto_splits(int(batch), int(num_heads), int(memory_max_len),
+                                                            int(num_tokens)))
+
+
+def decode_mla_chunk_workspace_bytes(batch, num_heads, memory_max_len, num_tokens, num_splits=0):
+    """Bytes of scratch flash_decode_mla_chunk needs (sfa_decode_mla_chunk_workspace_bytes); num_splits=0: the
+    library's choice."""
+    return int(_lib.load().sfa_decode_mla_chunk_workspace_bytes(int(batch), int(num_heads), int(memory_max_len),
+                                                                int(num_tokens), int(num_splits)))
+
+
+def _mla_args(q, kv_new, kv_cache, seq_len, o, tok, idx_layer, softmax_scale, rotary_cos_table, rotary_sin_table,
+              block_table, page_size):
+    """The checked sfa_mla_decode_args of flash_decode_mla (tok = (): q [B, H, 576]) and flash_decode_mla_chunk
+    (tok = (n,): q [B, n, H, 576]), num_splits and the workspace left open.  Returns (args, B, H, M)."""
+    what = "[B, " + "n, " * len(tok) + f"H, {MLA_DIM}]"
+    _require(isinstance(q, torch.Tensor) and q.dtype in _DTYPES and q.dim() == 3 + len(tok),
+             f"q must be a float16 or bfloat16 {what} tensor")
     dt, dev = q.dtype, q.device
-    B, H = int(q.shape[0]), int(q.shape[1])
-    _check_gpu_tensor(q, "q", dt, (B, H, MLA_DIM))
-    _check_gpu_tensor(kv_new, "kv_new", dt, (B, MLA_DIM), dev)
-    _check_gpu_tensor(o, "o", dt, (B, H, MLA_LATENT), dev)
+    B, H = int(q.shape[0]), int(q.shape[-2])
+    _check_gpu_tensor(q, "q", dt, (B, *tok, H, MLA_DIM))
+    _check_gpu_tensor(kv_new, "kv_new", dt, (B, *tok, MLA_DIM), dev)
+    _check_gpu_tensor(o, "o", dt, (B, *tok, H, MLA_LATENT), dev)
     _check_gpu_tensor(seq_len, "seq_len", torch.int32, (B,), dev)
     _require(isinstance(kv_cache, torch.Tensor) and kv_cache.dim() == 4,
              f"kv_cache must be [B, L, M, {MLA_DIM}], or with block_table [num_pages, L, page_size, {MLA_DIM}]")
@@ -623,11 +632,49 @@ def flash_decode_mla(q, kv_new, kv_cache, seq_len, o, *, idx_layer, softmax_scal
     a.batch_size, a.memory_max_len, a.num_heads, a.num_layer, a.idx_layer = B, M, H, L, int(idx_layer)
     a.dtype = _DTYPES[dt]
     a.softmax_scale = float(softmax_scale) if softmax_scale else 0.0
+    return a, B, H, M
+
+
+def flash_decode_mla(q, kv_new, kv_cache, seq_len, o, *, idx_layer, softmax_scale=None, num_splits=0,
+                     rotary_cos_table=None, rotary_sin_table=None, block_table=None, page_size=0):
+    """One decode step of multi-head latent attention in absorbed form (include/star_flash_attn.h, sfa_decode_mla).
+    q [B, H, 576] (512 absorbed no-rope dims, then 64 rope dims), kv_new [B, 576] (latent, then the rope key),
+    o [B, H, 512] (the latent output: the caller applies W_UV), seq_len int32 [B].  kv_cache: [B, L, M, 576], or with
+    block_table (int32 [B, pages_per_seq]) the pool [num_pages, L, page_size, 576]; memory_max_len is then
+    pages_per_seq * page_size.  H: a multiple of 16 in [16, 128].  softmax_scale None: 1/sqrt(576) -- pass the model's
+    own.  rotary tables: [memory_max_len, 32] of q's dtype, or None for in-kernel angles.  Returns `o`."""
+    lib = _lib.load()
+    a, B, H, M = _mla_args(q, kv_new, kv_cache, seq_len, o, (), idx_layer, softmax_scale, rotary_cos_table,
+                           rotary_sin_table, block_table, page_size)
+    dev = q.device
     with torch.cuda.device(dev):
         S = int(num_splits) if num_splits and num_splits > 0 else lib.sfa_decode_mla_auto_splits(B, H, M)
         ws = _workspace(dev, lib.sfa_decode_mla_workspace_bytes(B, H, M, S))
         a.num_splits, a.workspace, a.workspace_bytes = S, ws.data_ptr(), ws.numel()
         _lib.check(lib.sfa_decode_mla(ctypes.byref(a), _stream_ptr(dev)))
+        if _sync_checks:
+            check_decode_status(dev)
+    return o
+
+
+def flash_decode_mla_chunk(q, kv_new, kv_cache, seq_len, o, *, idx_layer, softmax_scale=None, num_splits=0,
+                           rotary_cos_table=None, rotary_sin_table=None, block_table=None, page_size=0):
+    """n new tokens per sequence of latent attention in one pass over the cache (sfa_decode_mla_chunk): what n successive
+    flash_decode_mla calls with seq_len advanced by one between them give -- token t is roped at seq_len[b] + t, stored
+    at that cache row and sees the history and the new tokens 0..t.  q [B, n, H, 576], kv_new [B, n, 576],
+    o [B, n, H, 512], n = q.shape[1] <= 32 (0: nothing is done); every other argument as in flash_decode_mla.
+    seq_len is not incremented: the caller advances it by the number of tokens it keeps.  Returns `o`."""
+    lib = _lib.load()
+    _require(isinstance(q, torch.Tensor) and q.dim() == 4, f"q must be a [B, n, H, {MLA_DIM}] tensor")
+    n = int(q.shape[1])
+    a, B, H, M = _mla_args(q, kv_new, kv_cache, seq_len, o, (n,), idx_layer, softmax_scale, rotary_cos_table,
+                           rotary_sin_table, block_table, page_size)
+    dev = q.device
+    with torch.cuda.device(dev):
+        S = int(num_splits) if num_splits and num_splits > 0 else lib.sfa_decode_mla_chunk_auto_splits(B, H, M, n)
+        ws = _workspace(dev, lib.sfa_decode_mla_chunk_workspace_bytes(B, H, M, n, S))
+        a.num_splits, a.workspace, a.workspace_bytes = S, ws.data_ptr(), ws.numel()
+        _lib.check(lib.sfa_decode_mla_chunk(ctypes.byref(a), n, _stream_ptr(dev)))
         if _sync_checks:
             check_decode_status(dev)
     return o
